@@ -2,6 +2,12 @@
 """bench.py -- FFWM flow-warp hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload train|flownet|flowtrain|warp|warpatt|ops]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed and K timed steps, writes the last timed step's outputs when --dump-outputs is given, and
+prints the lines below with the headline figure (metric / value / unit / ms_per_step).  Everything else -- the kernel rows of the
+captured step, the roofline copy probe, the `subpaths` legs, the stand-alone operator shapes, the CPU baseline, the all-reduce
+sweep of several ranks and the conv flop count -- runs only with --full (the --no-* switches still trim a --full run).
 
 Default workload = BASELINE.json configs[2]: the full FFWM train step (netG + netD + flowNetF + flowNetB, all losses,
 three Adam optimizers) on synthetic MultiPIE-shaped 128x128 tensors, batch 8 PER GPU (weak scaling; N > 1 is
@@ -10,7 +16,8 @@ on one batch resident in HBM.  fp32 throughout (the reference's dtype).  Rank 0 
 ({"kernels": [...]}, {"detail": {...}}) and then, as the LAST stdout line, ONE compact (< 4 KB) JSON object -- the line the
 driver parses -- with the contract's keys (emit_lines):
 
-  metric/value/unit : train img/s, whole job (W untimed steps, then exactly K steps between barrier + synchronize)
+  metric/value/unit : train img/s, whole job (W untimed steps, then exactly K steps between barrier + synchronize; one GPU: each
+                      step from the same set-up weights, timed by HIP events around it -- timed_from)
   roofline          : the SURVEY 8 a1-a6 kernel (warp / resample2d / block_extractor / local_attn_reshape family) that
                       moves the most algorithmic bytes inside the timed region: algorithmic bytes per launch / average
                       launch duration (HIP events on its launch stream, ffwm_prof_*) vs the 8 TB/s HBM peak;
@@ -32,6 +39,7 @@ Launch for N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N
                    --master-port P bench.py --gpus N --steps K --warmup W
 """
 import argparse
+import itertools
 import json
 import os
 import sys
@@ -201,7 +209,68 @@ def parse():
                          "run it eagerly (several ranks: hook-launched all-reduces overlapping backward)")
     ap.add_argument("--flownet-path", default="lean", choices=["lean", "module"],
                     help="flownet workload: the launch-lean eval path (BatchNorm folded, fused heads, hipGraph) or the nn.Module")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64; "
+                         "arrays above %d elements as a fixed seeded sample of that many)" % DUMP_SAMPLE)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: kernel rows and roofline probes, the subpaths, the "
+                         "stand-alone operator shapes, the CPU baseline, the all-reduce sweep, the conv flop count")
     return ap.parse_args()
+
+
+# ---- --dump-outputs -----------------------------------------------------------------------------------------------------
+DUMP_SAMPLE = 1 << 20            # elements kept of a larger array (4 MiB in float32)
+DUMP_LIMIT = 64 << 20            # bytes, all files together
+
+
+def dump_outputs(path, arrays):
+    """Write `arrays` ({name: tensor or float}) as path/<name>.npy.  Floating tensors keep float64 or become float32; an array of
+    more than DUMP_SAMPLE elements is reduced to the elements at DUMP_SAMPLE sorted indices drawn from a generator seeded by its
+    size, so that two runs (or two builds) with the same arguments write the same positions.  With the same arguments the inputs are
+    the same every run and so, up to the rounding of the kernels' float atomics, are the outputs (the train workload: fit_flow_identity,
+    timed_from)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, v in arrays.items():
+        if torch.is_tensor(v):
+            v = v.detach()
+            v = v.double() if v.dtype == torch.float64 else v.float()
+            flat = v.reshape(-1)
+            if flat.numel() > DUMP_SAMPLE:
+                g = torch.Generator().manual_seed(flat.numel())
+                idx = torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+                flat = flat[idx.to(flat.device)]
+                v = flat
+            a = v.cpu().numpy()
+        else:
+            a = np.asarray(v, dtype=np.float64)
+        total += a.nbytes
+        if total > DUMP_LIMIT:
+            raise RuntimeError("--dump-outputs: more than %d bytes" % DUMP_LIMIT)
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(arrays)
+
+
+def net_parameters(net):
+    """a network's parameters, flattened and concatenated in named_parameters() order"""
+    return torch.cat([p.detach().reshape(-1).float() for _, p in net.named_parameters()])
+
+
+def train_outputs(t):
+    """What the step computed from its inputs: its losses and the forward's images and flows (flowNetF's 128 px flow, netG's three
+    reconstructions, the guided-filter output).  The weights after its Adam update are left out: Adam divides every gradient by its
+    own running magnitude, so the float atomics' rounding in a gradient that is ~0 becomes a full-size update in either direction."""
+    def collect():
+        out = {"loss_" + k: float(v.detach()) for k, v in t.losses.items()}
+        for name in ("fake32", "fake64", "fake128", "img_GF128"):
+            if torch.is_tensor(getattr(t, name, None)):
+                out[name] = getattr(t, name).detach().clone()
+        flows = getattr(t, "flows_F", None)
+        if flows:
+            out["flow_F128"] = flows[0].detach().clone()
+        return out
+    return collect
 
 
 def init_dist(args):
@@ -225,6 +294,92 @@ def init_dist(args):
     if args.gpus != world and rank == 0 and world > 1:
         print("warning: --gpus %d but WORLD_SIZE %d" % (args.gpus, world), file=sys.stderr)
     return world, rank, local
+
+
+def fit_flow_identity(t, b, steps=80, lr=2e-3):
+    """FFWMTrainer.pretrain_flow_identity (the stand-in for the reference's pretrained flow nets: both nets fitted to the identity
+    sampling grid, Adam, `steps` steps, `lr`) made reproducible: the fit runs on plain copies of the nets through PyTorch's own
+    kernels (MIOpen off) with torch.use_deterministic_algorithms on -- an operation without a deterministic implementation raises --
+    and the fitted weights are loaded into the trainer's nets.  On the trainer's kernels the atomics' rounding, amplified by Adam,
+    leaves the fitted weights 8-11 % apart from run to run; MIOpen's deterministic mode alone still left them 3-5e-2 apart."""
+    from ffwm_amd import nets, trainer
+    def grid(s):
+        lin = (torch.arange(s, dtype=torch.float32, device=t.device) + 0.5) / s * 2 - 1
+        yy, xx = torch.meshgrid(lin, lin, indexing="ij")
+        return torch.stack((xx, yy), 0).unsqueeze(0)
+    targets = [grid(128), grid(64), grid(32)]
+    saved = (torch.backends.cudnn.enabled, torch.are_deterministic_algorithms_enabled(),
+             torch.is_deterministic_algorithms_warn_only_enabled())
+    torch.backends.cudnn.enabled = False
+    torch.use_deterministic_algorithms(True)
+    last = []
+    try:
+        for net in (t.flowNetF, t.flowNetB):
+            plain = nets.FlowNet(64).to(t.device)               # FFWMTrainer's flow nets (ngf = 64)
+            missing, _ = plain.load_state_dict(net.state_dict(), strict=False)
+            assert not set(missing) & set(n for n, _ in plain.named_parameters()), missing
+            params = [p for n, p in plain.named_parameters() if not n.startswith("inter_conv_occ")]
+            opt = torch.optim.Adam(params, lr=lr, foreach=False)
+            for _ in range(steps):
+                flows = plain(b["img_S"])
+                loss = sum((f - g).abs().mean() for f, g in zip(flows, targets))
+                opt.zero_grad(set_to_none=True)
+                loss.backward()
+                opt.step()
+            with torch.no_grad():
+                for n, p in net.named_parameters():
+                    p.copy_(plain.get_parameter(n))
+            last.append(float(loss.detach()))
+            del plain, opt
+    finally:
+        torch.backends.cudnn.enabled = saved[0]
+        torch.use_deterministic_algorithms(saved[1], warn_only=saved[2])
+    trainer.broadcast_module_state([t.flowNetF, t.flowNetB])
+    return last
+
+
+def state_snapshot(t):
+    """What a train step reads besides its batch: every float parameter and buffer of the four trained networks and the optimizers'
+    moments, device state (step counter, learning rate) and host step count -> (live tensors, their copies, optimizers, step counts)"""
+    opts = [o for o in (t.opt_F, t.opt_G, t.opt_D) if hasattr(o, "exp_avg")]
+    if len(opts) != 3:
+        raise RuntimeError("state_snapshot: the trainer's optimizers are not FlatAdam")
+    live = [x for name in t.MODEL_NAMES for x in itertools.chain(getattr(t, name).parameters(), getattr(t, name).buffers())
+            if x.is_floating_point()]
+    live += [x for o in opts for x in (o.exp_avg, o.exp_avg_sq, o.state) if x is not None]
+    return live, [x.detach().clone() for x in live], opts, [o.steps for o in opts]
+
+
+def timed_from(snapshot, step_fn, steps, warmup):
+    """One GPU: W untimed steps, then exactly K steps, each after the networks' weights, buffers and optimizer state are put back to
+    `snapshot`, so that every step computes from the same inputs.  Only the steps are timed (HIP events on the step's stream around
+    each step; the copy before it is outside); ms per step = their mean.  Returns (seconds of the K steps, launch-scope rows as
+    timed())."""
+    from ffwm_amd import _lib
+    live, saved, opts, counts = snapshot
+
+    def restore():
+        with torch.no_grad():
+            torch._foreach_copy_(live, saved)
+        for o, n in zip(opts, counts):
+            o.steps = n
+    for _ in range(warmup):
+        restore()
+        step_fn()
+    torch.cuda.synchronize()
+    _lib.prof_reset()
+    _lib.prof_enable(True)
+    evs = []
+    for _ in range(steps):
+        restore()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        step_fn()
+        b.record()
+        evs.append((a, b))
+    torch.cuda.synchronize()
+    _lib.prof_enable(False)
+    return sum(a.elapsed_time(b) for a, b in evs) * 1e-3, _lib.prof_collect()
 
 
 def timed(step_fn, steps, warmup, world):
@@ -586,9 +741,10 @@ def _top_kernels(rows, passes, n):
     return [[r["kernel"], round(r["launches"] / passes, 1), round(r["total_ms"] / passes * 1e3, 1)] for r in rows]
 
 
-def run_warp_attention(dev, bs, steps, warmup, world, seed=1, graph=True, route=True):
+def run_warp_attention(dev, bs, steps, warmup, world, seed=1, graph=True, route=True, kernel_rows_after=True, keep=False):
     """netG's warp-attention module alone (base_networks.py:323-333): warp + flip + cat (HIP) -> att convs -> multiply,
-    three levels, batch `bs`.  Returns forward-only and forward + backward figures."""
+    three levels, batch `bs`.  Returns forward-only and forward + backward figures.  kernel_rows_after: (graph) time the hand-written
+    kernels in eager passes after the timed region; keep: also return copies of the gradients of the last timed pass."""
     from ffwm_amd import flops, nets
     torch.manual_seed(0)
     mod = nets.WarpAttention(sn=True).to(dev).train()
@@ -628,16 +784,28 @@ def run_warp_attention(dev, bs, steps, warmup, world, seed=1, graph=True, route=
             fn()
         return gr.replay
 
+    def last_pass():
+        if not keep:
+            return {}
+        out = {"grad_feat%d" % i: t.grad.clone() for i, t in enumerate(feats)}
+        out.update({"grad_flow%d" % i: t.grad.clone() for i, t in enumerate(flows)})
+        out["grad_params"] = torch.cat([p.grad.reshape(-1).float() for p in mod.parameters() if p.grad is not None])
+        return out
+
     if graph:
         dt_f, _ = timed(replayed(fwd), steps, warmup, world)
-        dt_b, _ = timed(replayed(fwd_bwd), steps, warmup, world)
+        dt_b, rows_b = timed(replayed(fwd_bwd), steps, warmup, world)
         torch.cuda.synchronize(dev)
-        # HIP events cannot bracket kernels inside a replayed graph: the per-kernel rows come from eager passes afterwards
-        _, rows_f = timed(fwd, 3, 1, world)
-        _, rows_b = timed(fwd_bwd, 3, 1, world)
+        last = last_pass()
+        rows_f = {}
+        if kernel_rows_after:
+            # HIP events cannot bracket kernels inside a replayed graph: the per-kernel rows come from eager passes afterwards
+            _, rows_f = timed(fwd, 3, 1, world)
+            _, rows_b = timed(fwd_bwd, 3, 1, world)
     else:
         dt_f, rows_f = timed(fwd, steps, warmup, world)
         dt_b, rows_b = timed(fwd_bwd, steps, warmup, world)
+        last = last_pass()
     imgs = bs * world * steps
     ceil_fb = FP32_PEAK / (fl["total"] / bs)
     return {"scope": "warp + flip + cat (HIP) + attention convs (conv block + sigmoid residual block, spectral norm) + multiply; "
@@ -656,7 +824,7 @@ def run_warp_attention(dev, bs, steps, warmup, world, seed=1, graph=True, route=
             # where a forward + backward pass goes: the hand-written kernels with the most time per pass (HIP events of 3 eager passes,
             # [kernel, launches per pass, us per pass]) and their sum beside the replayed pass's wall time -- the rest is vendor / ATen
             "top5": _top_kernels(kernel_rows(rows_b, "warp_attention fwd+bwd"), 3, 5),
-            "own_kernel_ms_per_pass": round(sum(r["total_ms"] for r in kernel_rows(rows_b, "warp_attention fwd+bwd")) / 3, 3)}, dt_b, rows_b
+            "own_kernel_ms_per_pass": round(sum(r["total_ms"] for r in kernel_rows(rows_b, "warp_attention fwd+bwd")) / 3, 3)}, dt_b, rows_b, last
 
 
 def run_flownet(dev, bs, steps, warmup, world, path, seed=1):
@@ -666,21 +834,22 @@ def run_flownet(dev, bs, steps, warmup, world, path, seed=1):
     x = torch.rand(bs, 3, 128, 128, generator=torch.Generator().manual_seed(seed)).to(dev)
     with torch.no_grad():
         fl = flops.count_step([net], lambda: net(x))
+    last = {}
     if path == "lean":
         from ffwm_amd import flownet_eval
         lean = flownet_eval.FoldedFlowNet(net, graph=True)
 
         def step():
-            lean(x)
+            last["flows"] = lean(x)
     else:
         def step():
             with torch.no_grad():
-                net(x)
+                last["flows"] = net(x)
     dt, rows = timed(step, steps, warmup, world)
     imgs = bs * world * steps
     return {"img_per_s": round(imgs / dt, 1), "ms_per_fwd": round(dt / steps * 1e3, 4), "batch": bs, "path": path,
             "conv_GFLOP_per_img": round(fl["fwd"] / bs / 1e9, 3),
-            "fp32_flop_frac": round(imgs / dt / world * fl["fwd"] / bs / FP32_PEAK, 5)}, dt, rows
+            "fp32_flop_frac": round(imgs / dt / world * fl["fwd"] / bs / FP32_PEAK, 5)}, dt, rows, last
 
 
 def main():
@@ -703,6 +872,7 @@ def main():
               "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic"}
     extras = {}
     t = None
+    outputs = None          # () -> {name: tensor or float}: what the last timed step computed (--dump-outputs), taken right after timing
 
     if args.workload == "train":
         from ffwm_amd import flops, trainer
@@ -711,14 +881,18 @@ def main():
                                 bucket_bytes=args.bucket_mb << 20, capturable=args.graph == "on",
                                 mfma_wgrad=args.mfma_wgrad == "on")
         batch = trainer.synthetic_batch(bs, dev, seed=1 + rank)
-        flow_fit = t.pretrain_flow_identity(batch) if args.flow_init == "fit-identity" else None
+        flow_fit = fit_flow_identity(t, batch) if args.flow_init == "fit-identity" else None
+        # one GPU: every warm-up and timed step starts from the weights set up so far (see timed_from)
+        snapshot = state_snapshot(t) if world == 1 else None
         graphed = args.graph == "on"
         nets_all = [t.flowNetF, t.flowNetB, t.netG, t.netD, t.lightCNN, t.vgg]
+        step_flops = None
         if graphed:            # count on a throw-away eager trainer: hooks + an eager step before capture() must not touch the graphed one
-            tc = trainer.FFWMTrainer(dev, world_size=1, seed=0, titers=args.titers, mfma_wgrad=args.mfma_wgrad == "on")
-            step_flops = flops.count_step([tc.flowNetF, tc.flowNetB, tc.netG, tc.netD, tc.lightCNN, tc.vgg],
-                                          lambda: tc.step(batch, batch_increment=0))
-            del tc
+            if args.full:
+                tc = trainer.FFWMTrainer(dev, world_size=1, seed=0, titers=args.titers, mfma_wgrad=args.mfma_wgrad == "on")
+                step_flops = flops.count_step([tc.flowNetF, tc.flowNetB, tc.netG, tc.netD, tc.lightCNN, tc.vgg],
+                                              lambda: tc.step(batch, batch_increment=0))
+                del tc
         else:
             step_flops = flops.count_step(nets_all, lambda: t.step(batch, batch_increment=0))       # one untimed eager step
         capture_mode, d_side, dp_spread = None, False, None
@@ -743,7 +917,7 @@ def main():
                 if t is None:
                     t = trainer.FFWMTrainer(dev, world_size=world, seed=0, titers=args.titers, bucket_bytes=args.bucket_mb << 20,
                                             capturable=True, mfma_wgrad=args.mfma_wgrad == "on")
-                    flow_fit = t.pretrain_flow_identity(batch) if args.flow_init == "fit-identity" else None
+                    flow_fit = fit_flow_identity(t, batch) if args.flow_init == "fit-identity" else None
                 ok = True
                 try:
                     t.capture(batch, warmup=max(2, args.warmup), mode=mode)
@@ -776,10 +950,15 @@ def main():
                 args.graph = "off"
                 t = trainer.FFWMTrainer(dev, world_size=world, seed=0, titers=args.titers, bucket_bytes=args.bucket_mb << 20,
                                         capturable=False, mfma_wgrad=args.mfma_wgrad == "on")
-                flow_fit = t.pretrain_flow_identity(batch) if args.flow_init == "fit-identity" else None
+                flow_fit = fit_flow_identity(t, batch) if args.flow_init == "fit-identity" else None
             nets_all = [t.flowNetF, t.flowNetB, t.netG, t.netD, t.lightCNN, t.vgg]
-        dt, rows = timed(lambda: t.step(batch, batch_increment=0), args.steps, args.warmup, world)
-        if graphed:
+        if snapshot is not None:
+            dt, rows = timed_from(snapshot, lambda: t.step(batch, batch_increment=0), args.steps, args.warmup)
+        else:
+            dt, rows = timed(lambda: t.step(batch, batch_increment=0), args.steps, args.warmup, world)
+        if args.dump_outputs:
+            outputs = train_outputs(t)()
+        if graphed and args.full:
             # HIP events cannot bracket kernels inside a replayed graph: time the hand-written kernels
             # in two EAGER steps of the same trainer right after the timed region -- on ONE stream: beside the side streams'
             # kernels a launch shares the chip and the event pair around it measures the sharing, not the kernel (round 4: with the
@@ -790,7 +969,6 @@ def main():
             t.set_side_streams(True)
             result["kernel_rows_from"] = "2 eager single-stream steps after the timed region (events cannot bracket kernels of a replayed graph)"
         imgs = bs * world * args.steps
-        own = step_flops["total"] / bs
         result.update({"metric": "train img/s (128x128, full FFWM GAN step)", "value": round(imgs / dt, 2),
                        "unit": "img/s", "ms_per_step": round(dt / args.steps * 1e3, 3),
                        "config": {"workload": "BASELINE configs[2]: full FFWM train step (netG+netD+flowNetF+flowNetB, "
@@ -822,17 +1000,19 @@ def main():
                                                 "pretrained flowNetF/B checkpoints), final L1 %s" % [round(v, 3) for v in flow_fit])
                                   if flow_fit else "randomly initialised"},
                        "img_per_s_per_gpu": round(imgs / dt / world, 2),
-                       "conv_GFLOP_per_img": {"this_step": round(own / 1e9, 1), "fwd": round(step_flops["fwd"] / bs / 1e9, 1),
-                                              "bwd": round(step_flops["bwd"] / bs / 1e9, 1),
-                                              "reference_step_estimate": REF_TRAIN_FLOP_PER_IMG / 1e9,
-                                              "note": "counted over every conv / linear call of one step (ffwm_amd/flops.py); "
-                                                      "lower than the reference's estimate because frozen LightCNN / VGG19 get no "
-                                                      "weight gradients, target-side extractors run under no_grad and the LightCNN "
-                                                      "passes are deduplicated (result-preserving)"},
-                       "fp32_flop_frac": round(imgs / dt / world * own / FP32_PEAK, 4),
-                       "fp32_ceiling_img_per_s_per_gpu": round(FP32_PEAK / own, 1),
                        "losses": {k: round(v, 5) for k, v in t.loss_values().items()}})
-        if world > 1:
+        if step_flops is not None:
+            own = step_flops["total"] / bs
+            result.update({"conv_GFLOP_per_img": {"this_step": round(own / 1e9, 1), "fwd": round(step_flops["fwd"] / bs / 1e9, 1),
+                                                  "bwd": round(step_flops["bwd"] / bs / 1e9, 1),
+                                                  "reference_step_estimate": REF_TRAIN_FLOP_PER_IMG / 1e9,
+                                                  "note": "counted over every conv / linear call of one step (ffwm_amd/flops.py); "
+                                                          "lower than the reference's estimate because frozen LightCNN / VGG19 get no "
+                                                          "weight gradients, target-side extractors run under no_grad and the LightCNN "
+                                                          "passes are deduplicated (result-preserving)"},
+                           "fp32_flop_frac": round(imgs / dt / world * own / FP32_PEAK, 4),
+                           "fp32_ceiling_img_per_s_per_gpu": round(FP32_PEAK / own, 1)})
+        if world > 1 and args.full:
             # what the collectives cost when nothing overlaps them (outside the timed region, device idle): every bucket of the
             # G-step set on its own, and a message-size sweep that shows where the ring saturates the xGMI links
             try:
@@ -851,7 +1031,8 @@ def main():
         result["config"]["bucket_MiB"] = args.bucket_mb
     elif args.workload == "flownet":
         bs = args.batch or 6
-        r, dt, rows = run_flownet(dev, bs, args.steps, args.warmup, world, args.flownet_path, seed=1 + rank)
+        r, dt, rows, last = run_flownet(dev, bs, args.steps, args.warmup, world, args.flownet_path, seed=1 + rank)
+        outputs = {"flow%d" % i: f for i, f in enumerate(last["flows"])}
         result.update({"metric": "FlowNetF forward img/s (128x128)", "value": r["img_per_s"], "unit": "img/s",
                        "ms_per_step": round(dt / args.steps * 1e3, 4),
                        "config": {"workload": "BASELINE configs[1]: FlowNetF forward-only, bs=%d" % bs, "path": args.flownet_path,
@@ -880,6 +1061,9 @@ def main():
                 graphed = False
                 ft = trainer.FlowNetTrainer(dev, world_size=world, seed=0, bucket_bytes=args.bucket_mb << 20)
         dt, rows = timed(lambda: ft.step(batch), args.steps, args.warmup, world)
+        if args.dump_outputs:
+            outputs = {"loss_" + k: float(v.detach()) for k, v in ft.losses.items()}
+            outputs["flowNet_params"] = net_parameters(ft.flowNet)
         imgs = bs * world * args.steps
         result.update({"metric": "FlowNet pre-training img/s (128x128)", "value": round(imgs / dt, 2), "unit": "img/s",
                        "ms_per_step": round(dt / args.steps * 1e3, 3),
@@ -890,8 +1074,9 @@ def main():
                        "losses": {k: round(v, 5) for k, v in ft.loss_values().items()}})
     elif args.workload == "warpatt":
         bs = args.batch or 8
-        r, dt, rows = run_warp_attention(dev, bs, args.steps, args.warmup, world, seed=1 + rank, graph=args.graph == "on",
-                                          route=os.environ.get("FFWM_WARPATT_ROUTE", "1") != "0")
+        r, dt, rows, outputs = run_warp_attention(dev, bs, args.steps, args.warmup, world, seed=1 + rank, graph=args.graph == "on",
+                                                  route=os.environ.get("FFWM_WARPATT_ROUTE", "1") != "0", kernel_rows_after=args.full,
+                                                  keep=bool(args.dump_outputs))
         result.update({"metric": "warp+attention path img/s (3 netG levels, fwd+bwd)", "value": r["fwd_bwd_img_per_s"], "unit": "img/s",
                        "ms_per_step": r["fwd_bwd_ms"],
                        "config": {"workload": "netG warp-attention module (base_networks.py:323-333), 3 levels, fwd+bwd", "batch_per_gpu": bs,
@@ -905,12 +1090,20 @@ def main():
         flows = [smooth_flow(bs, s).to(dev).requires_grad_(True) for s in (32, 64, 128)]
         gos = [torch.rand(bs, 2 * c, s, s, generator=g).to(dev) for c, s in ((128, 32), (64, 64), (64, 128))]
         mod = WarpFlipCat()
+        keep = [None] * len(feats) if args.dump_outputs else None
 
         def step():
-            for f, fl, go in zip(feats, flows, gos):
+            for i, (f, fl, go) in enumerate(zip(feats, flows, gos)):
                 f.grad = fl.grad = None
-                mod(f, fl).backward(go)
+                y = mod(f, fl)
+                y.backward(go)
+                if keep is not None:
+                    keep[i] = y
         dt, rows = timed(step, args.steps, args.warmup, world)
+        if keep is not None:
+            outputs = {}
+            for i, (y, f, fl) in enumerate(zip(keep, feats, flows)):
+                outputs.update({"out%d" % i: y, "grad_feat%d" % i: f.grad, "grad_flow%d" % i: fl.grad})
         imgs = bs * world * args.steps
         result.update({"metric": "warp+flip+cat kernels img/s (3 netG levels, fwd+bwd)", "value": round(imgs / dt, 2),
                        "unit": "img/s", "ms_per_step": round(dt / args.steps * 1e3, 3),
@@ -931,6 +1124,7 @@ def main():
             gf.zero_()
             ops.block_extractor_backward(src, flow, out, 3, gs, gf)
         dt, rows = timed(step, args.steps, args.warmup, world)
+        outputs = {"out": out, "grad_src": gs, "grad_flow": gf}
         imgs = bs * world * args.steps
         result.update({"metric": "block_extractor fwd+bwd img/s (256x256, C=128, k=3)", "value": round(imgs / dt, 2),
                        "unit": "img/s", "ms_per_step": round(dt / args.steps * 1e3, 3),
@@ -938,17 +1132,21 @@ def main():
                                   "parallelism": "dp%d" % world}})
 
     # ---- the other scopes of SURVEY 8(d), N = 1 only (they do not take part in the scaling curve)
-    if args.workload == "train" and world == 1 and not args.no_extras:
+    if args.dump_outputs and outputs is not None:
+        torch.cuda.synchronize()
+        dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, "rank%d" % rank), outputs)
+
+    if args.workload == "train" and world == 1 and args.full and not args.no_extras:
         from ffwm_amd import trainer
         bs = args.batch or 8
         try:
-            r, _, _ = run_warp_attention(dev, bs, 20, 5, world)
+            r, _, _, _ = run_warp_attention(dev, bs, 20, 5, world)
             extras["warp_attention_path"] = r
         except Exception as e:
             extras["warp_attention_path"] = {"error": repr(e)}
         for path in ("lean", "module"):
             try:
-                r, _, _ = run_flownet(dev, 6, 30, 10, world, path)
+                r, _, _, _ = run_flownet(dev, 6, 30, 10, world, path)
                 extras["flownet_fwd_cfg2" if path == "lean" else "flownet_fwd_cfg2_module_path"] = r
             except Exception as e:
                 extras["flownet_fwd_cfg2" if path == "lean" else "flownet_fwd_cfg2_module_path"] = {"error": repr(e)}
@@ -1013,34 +1211,35 @@ def main():
             result["roofline"] = roofline_row(max(hot, key=lambda r: r["alg_MB"] * r["launches"]), "hbm")
             result["roofline"].update(hot_rows_summary(inrun))
             result["roofline"].pop("kernels", None)
-            try:
-                # context for a launch of this SIZE: torch's copy_ moving the same number of bytes (half read, half written), timed the
-                # same way on warm caches and after a 1 GiB fill (the cache state an in-step launch finds) -- tools/stream_probe.py
-                nbytes = int(result["roofline"]["alg_MB_per_launch"] * 1e6)
-                src = torch.rand(nbytes // 8, device=dev)
-                dst = torch.empty_like(src)
-                big = torch.empty(256 << 20, device=dev)
+            if args.full:
+                try:
+                    # context for a launch of this SIZE: torch's copy_ moving the same number of bytes (half read, half written), timed the
+                    # same way on warm caches and after a 1 GiB fill (the cache state an in-step launch finds) -- tools/stream_probe.py
+                    nbytes = int(result["roofline"]["alg_MB_per_launch"] * 1e6)
+                    src = torch.rand(nbytes // 8, device=dev)
+                    dst = torch.empty_like(src)
+                    big = torch.empty(256 << 20, device=dev)
 
-                def copy_us(cold, n=8):
-                    dst.copy_(src)
-                    torch.cuda.synchronize()
-                    tot = 0.0
-                    for _ in range(n):
-                        if cold:
-                            big.fill_(1.0)
-                        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        a.record()
+                    def copy_us(cold, n=8):
                         dst.copy_(src)
-                        b.record()
                         torch.cuda.synchronize()
-                        tot += a.elapsed_time(b)
-                    return tot / n * 1e3
-                warm, cold = copy_us(False), copy_us(True)
-                result["roofline"]["copy_same_bytes_us"] = {"warm": round(warm, 1), "cold": round(cold, 1)}
-                result["roofline"]["copy_same_bytes_frac_cold"] = round(nbytes / (cold * 1e-6) / HBM_PEAK, 4)
-                del src, dst, big
-            except Exception as e:
-                result["roofline"]["copy_same_bytes_us"] = {"error": repr(e)}
+                        tot = 0.0
+                        for _ in range(n):
+                            if cold:
+                                big.fill_(1.0)
+                            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                            a.record()
+                            dst.copy_(src)
+                            b.record()
+                            torch.cuda.synchronize()
+                            tot += a.elapsed_time(b)
+                        return tot / n * 1e3
+                    warm, cold = copy_us(False), copy_us(True)
+                    result["roofline"]["copy_same_bytes_us"] = {"warm": round(warm, 1), "cold": round(cold, 1)}
+                    result["roofline"]["copy_same_bytes_frac_cold"] = round(nbytes / (cold * 1e-6) / HBM_PEAK, 4)
+                    del src, dst, big
+                except Exception as e:
+                    result["roofline"]["copy_same_bytes_us"] = {"error": repr(e)}
         elif other_hbm:
             result["roofline"] = roofline_row(max(other_hbm, key=lambda r: r["alg_MB"] * r["launches"]), "hbm")
         else:
@@ -1071,12 +1270,12 @@ def main():
         if other_hbm and hot:
             result["roofline_hbm_other"] = roofline_row(max(other_hbm, key=lambda r: r["alg_MB"] * r["launches"]), "hbm")
         result["kernels"] = inrun
-        if not args.no_kernels:
+        if args.full and not args.no_kernels:
             result["kernels"] = inrun + standalone_kernels()
         for row in result["kernels"]:
             if row["kernel"] in traffic and row["where"] == "timed region":
                 row["pmc_traffic_MB"] = round(traffic[row["kernel"]]["traffic_bytes"] / 1e6, 3)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 result.update(cpu_train_baseline(args.titers) if args.workload in ("train",) else cpu_ops_baseline())
             except Exception as e:      # the baseline leg must never take the measurement down

@@ -1,6 +1,6 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 for o in "warp_multi_lds=1" "warp_multi_lds=0" "warp_multi_lds=2" "warp_multi_lds=1" "warp_multi_lds=0"; do
-  FFWM_OPTS=$o python $R/bench.py --steps 12 --warmup 3 --no-cpu-baseline --no-extras --no-kernels 2>/dev/null > /tmp/o.txt
+  FFWM_OPTS=$o python $R/bench.py --full --steps 12 --warmup 3 --no-cpu-baseline --no-extras --no-kernels 2>/dev/null > /tmp/o.txt
   python - "$o" <<'P'
 import json,sys
 L=open("/tmp/o.txt").read().strip().splitlines()

@@ -3,7 +3,7 @@ import json, os, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for dg, wg in (("0", "0"), ("1", "1")):
     env = dict(os.environ, FFWM_CONV_DGRAD=dg, FFWM_CONV_WGRAD=wg)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "8", "--warmup", "3", "--no-cpu-baseline", "--no-kernels", "--no-extras"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "8", "--warmup", "3", "--no-cpu-baseline", "--no-kernels", "--no-extras"],
                          env=env, capture_output=True, text=True).stdout.strip().splitlines()[-1]
     d = json.loads(out)
     print("dgrad=%s wgrad=%s: %.2f img/s, %.2f ms/step" % (dg, wg, d["value"], d["ms_per_step"]))

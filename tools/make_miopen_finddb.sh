@@ -10,7 +10,7 @@ rm -rf $DB && mkdir -p $DB
 cp $R/ffwm_amd/miopen_db/*.txt $DB/ 2>/dev/null
 export MIOPEN_USER_DB_PATH=$DB
 for w in ${FFWM_FIND_WORKLOADS:-train flownet flowtrain}; do
-    FFWM_MIOPEN_FIND=1 timeout 1300 python $R/bench.py --workload $w --steps 3 --warmup 2 --no-cpu-baseline --no-kernels 2>/dev/null | tail -1 | cut -c1-160
+    FFWM_MIOPEN_FIND=1 timeout 1300 python $R/bench.py --full --workload $w --steps 3 --warmup 2 --no-cpu-baseline --no-kernels 2>/dev/null | tail -1 | cut -c1-160
 done
 rm -f $DB/*.time
 ls -la $DB; du -sh $DB

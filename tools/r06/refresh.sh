@@ -16,10 +16,10 @@ rm -rf $OUT && mkdir -p $OUT
 trace() {   # tag window-ms extra-steady-args -- bench-args...
   local TAG=$1 WIN=$2 EXTRA=$3; shift; shift; shift
   rm -rf /tmp/kt_$TAG && mkdir -p /tmp/kt_$TAG
-  timeout 900 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt_$TAG -- python $R/bench.py "$@" --no-cpu-baseline --no-extras > $OUT/${TAG}_bench.log 2>&1
+  timeout 900 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt_$TAG -- python $R/bench.py --full "$@" --no-cpu-baseline --no-extras > $OUT/${TAG}_bench.log 2>&1
   local F=$(find /tmp/kt_$TAG -name "*kernel_trace.csv" | head -1)
   python $R/tools/steady_stats.py $F $OUT/${TAG}_kernel_stats.csv --window-ms $WIN $EXTRA \
-      --header "rocprofv3 --kernel-trace -- python bench.py $* --no-cpu-baseline --no-extras; steady_stats.py --window-ms $WIN $EXTRA (tools/r06/refresh.sh)" > $OUT/${TAG}_steady.log 2>&1
+      --header "rocprofv3 --kernel-trace -- python bench.py --full $* --no-cpu-baseline --no-extras; steady_stats.py --window-ms $WIN $EXTRA (tools/r06/refresh.sh)" > $OUT/${TAG}_steady.log 2>&1
   grep -h '^{' $OUT/${TAG}_bench.log | tail -1 > $OUT/${TAG}_bench.json
 }
 trace train_step 200 "" --steps 6 --warmup 3 --no-kernels
@@ -31,11 +31,11 @@ trace flownet 15 "" --workload flownet --steps 40 --warmup 10 --no-kernels
 trace flowtrain 60 "" --workload flowtrain --steps 10 --warmup 3 --no-kernels
 # whole-run statistics of the hand-written kernels of the default command in eager mode (train steps + stand-alone shapes)
 rm -rf /tmp/kt_all && mkdir -p /tmp/kt_all
-timeout 900 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt_all -- python $R/bench.py --graph off --steps 6 --warmup 3 --no-cpu-baseline --no-extras > $OUT/trace_all.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt_all -- python $R/bench.py --full --graph off --steps 6 --warmup 3 --no-cpu-baseline --no-extras > $OUT/trace_all.log 2>&1
 python $R/tools/steady_stats.py $(find /tmp/kt_all -name "*kernel_trace.csv" | head -1) $OUT/ffwm_kernels_whole_run.csv --window-ms 0 --by-shape --include "ffwm::" \
-    --header "hand-written kernels over the whole traced run, per launch geometry: rocprofv3 --kernel-trace -- python bench.py --graph off --steps 6 --warmup 3 --no-cpu-baseline --no-extras" > /dev/null 2>&1
+    --header "hand-written kernels over the whole traced run, per launch geometry: rocprofv3 --kernel-trace -- python bench.py --full --graph off --steps 6 --warmup 3 --no-cpu-baseline --no-extras" > /dev/null 2>&1
 # counter passes
-PMC="python $R/bench.py --graph off --steps 2 --warmup 2 --no-cpu-baseline --no-extras"
+PMC="python $R/bench.py --full --graph off --steps 2 --warmup 2 --no-cpu-baseline --no-extras"
 i=0
 for C in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_INST_LDS SQ_INSTS_SALU"; do
   rm -rf /tmp/pmc_$i && mkdir -p /tmp/pmc_$i
@@ -50,9 +50,9 @@ for j in 0 1; do
   timeout 300 rocprofv3 --pmc $C --kernel-include-regex "bias_act" --kernel-trace --output-format csv -d /tmp/pmc_cal_$j -- python $R/tools/pmc_calib.py > $OUT/pmc_calib_pass$j.log 2>&1
 done
 python $R/tools/pmc_fold.py $OUT/pmc_calibration_raw.json /tmp/pmc_cal_0 /tmp/pmc_cal_1 > $OUT/pmc_calib_fold.txt 2>&1
-timeout 1200 python $R/bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout 1200 python $R/bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 tail -c 300 $OUT/bench_default.json
-timeout 900 python $R/bench.py --graph off --no-cpu-baseline --no-kernels --no-extras > $OUT/bench_eager.json 2>/dev/null
+timeout 900 python $R/bench.py --full --graph off --no-cpu-baseline --no-kernels --no-extras > $OUT/bench_eager.json 2>/dev/null
 timeout 600 python $R/tools/wino_check.py 2>&1 | grep -v amdgpu.ids > $OUT/winograd_vs_vendor.txt
 (cd $R && timeout 900 python tools/ref_vs_hip.py > $OUT/ref_vs_hip.log 2>&1; cp gpurun_out/ref_vs_hip.json $OUT/ref_vs_hip.json)
 ls -la $OUT | head -50

@@ -5,7 +5,7 @@
 #   3. counter passes of the default command, hand-written kernels only (--kernel-include-regex ffwm: a counter pass
 #      that also instruments MIOpen's kernels aborts with HSA_STATUS_ERROR_INVALID_PACKET_FORMAT): FETCH_SIZE, WRITE_SIZE
 #      and two SQ sets in SEPARATE runs (counters + --kernel-trace only)
-#   4. the default `python bench.py` line
+#   4. the default `python bench.py --full` line
 # Everything lands in gpurun_out/refresh/ (small CSV / JSON only); tools/fold_profiles.py turns it into profiles/r05_*.
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
@@ -14,17 +14,17 @@ rm -rf $OUT && mkdir -p $OUT
 trace() {   # tag window-ms bench-args...
   local TAG=$1 WIN=$2; shift; shift
   rm -rf /tmp/kt_$TAG && mkdir -p /tmp/kt_$TAG
-  timeout 900 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt_$TAG -- python $R/bench.py "$@" --no-cpu-baseline --no-kernels --no-extras > $OUT/${TAG}_bench.log 2>&1
+  timeout 900 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt_$TAG -- python $R/bench.py --full "$@" --no-cpu-baseline --no-kernels --no-extras > $OUT/${TAG}_bench.log 2>&1
   local F=$(find /tmp/kt_$TAG -name "*kernel_trace.csv" | head -1)
   python $R/tools/steady_stats.py $F $OUT/${TAG}_kernel_stats.csv --window-ms $WIN \
-      --header "rocprofv3 --kernel-trace -- python bench.py $* --no-cpu-baseline --no-kernels --no-extras; last $WIN ms of the trace (tools/refresh_profiles.sh)" > $OUT/${TAG}_steady.log 2>&1
+      --header "rocprofv3 --kernel-trace -- python bench.py --full $* --no-cpu-baseline --no-kernels --no-extras; last $WIN ms of the trace (tools/refresh_profiles.sh)" > $OUT/${TAG}_steady.log 2>&1
   grep -h '^{' $OUT/${TAG}_bench.log | tail -1 > $OUT/${TAG}_bench.json
 }
 trace train_step 200 --steps 6 --warmup 3
 # per-STEP accounting of the same trace (the default = captured step, several streams) and of an eager, single-graph-less run
 python $R/tools/step_trace.py $(find /tmp/kt_train_step -name "*kernel_trace.csv" | head -1) --steps 3 --top 60 > $OUT/train_step_per_step.txt 2>&1
 rm -rf /tmp/kt_eager && mkdir -p /tmp/kt_eager
-timeout 900 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt_eager -- python $R/bench.py --graph off --steps 6 --warmup 3 --no-cpu-baseline --no-kernels --no-extras > $OUT/train_eager_bench.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt_eager -- python $R/bench.py --full --graph off --steps 6 --warmup 3 --no-cpu-baseline --no-kernels --no-extras > $OUT/train_eager_bench.log 2>&1
 python $R/tools/step_trace.py $(find /tmp/kt_eager -name "*kernel_trace.csv" | head -1) --steps 3 --top 60 > $OUT/train_step_eager_per_step.txt 2>&1
 trace warpatt 30 --workload warpatt --steps 20 --warmup 5
 trace warp 10 --workload warp --steps 40 --warmup 10
@@ -34,7 +34,7 @@ trace flowtrain 60 --workload flowtrain --steps 10 --warmup 3
 trace ops 30 --workload ops --steps 10 --warmup 3
 # whole-run statistics of the hand-written kernels of the default command (train steps + stand-alone cfg-1 / cfg-5 shapes)
 rm -rf /tmp/kt_all && mkdir -p /tmp/kt_all
-timeout 900 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt_all -- python $R/bench.py --graph off --steps 6 --warmup 3 --no-cpu-baseline --no-extras > $OUT/trace_all.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt_all -- python $R/bench.py --full --graph off --steps 6 --warmup 3 --no-cpu-baseline --no-extras > $OUT/trace_all.log 2>&1
 F=$(find /tmp/kt_all -name "*kernel_trace.csv" | head -1)
 python - "$F" "$OUT/ffwm_kernels_whole_run.csv" <<'PY'
 import collections, csv, sys
@@ -47,13 +47,13 @@ for r in csv.DictReader(open(sys.argv[1])):
     a[0] += 1
     a[1] += int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
 with open(sys.argv[2], "w") as f:
-    f.write("# hand-written kernels over the whole traced run (train steps + stand-alone cfg-1 / cfg-5 shapes), rocprofv3 --kernel-trace -- python bench.py --steps 6 --warmup 3 --no-cpu-baseline --no-extras\n")
+    f.write("# hand-written kernels over the whole traced run (train steps + stand-alone cfg-1 / cfg-5 shapes), rocprofv3 --kernel-trace -- python bench.py --full --steps 6 --warmup 3 --no-cpu-baseline --no-extras\n")
     f.write("Name,Calls,TotalDurationNs,AverageNs\n")
     for n, (c, t) in sorted(acc.items(), key=lambda kv: -kv[1][1]):
         f.write('"%s",%d,%d,%d\n' % (n, c, t, t // c))
 PY
 # counter passes
-PMC="python $R/bench.py --graph off --steps 2 --warmup 2 --no-cpu-baseline --no-extras"
+PMC="python $R/bench.py --full --graph off --steps 2 --warmup 2 --no-cpu-baseline --no-extras"
 i=0
 for C in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_INST_LDS SQ_INSTS_SALU"; do
   rm -rf /tmp/pmc_$i && mkdir -p /tmp/pmc_$i
@@ -61,7 +61,7 @@ for C in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ
   i=$((i+1))
 done
 python $R/tools/pmc_fold.py $OUT/bench_pmc_raw.json /tmp/pmc_0 /tmp/pmc_1 /tmp/pmc_2 /tmp/pmc_3 > $OUT/pmc_fold.txt 2>&1
-timeout 1200 python $R/bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout 1200 python $R/bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 tail -c 400 $OUT/bench_default.json
 # SQ / memory counters of the Winograd convolution kernel alone (netG's 192 -> 192 and 256 -> 256 layers at 128 x 128, batch 8)
 for CK in 192 256; do
@@ -73,7 +73,7 @@ python $R/tools/wino_layers.py > $OUT/winograd_layers_of_the_step.txt 2>/dev/nul
 
 # round 3: the eager line beside the default (captured) one, every layer's backward vs the vendor's, the in-step warp sweep, switches A/B,
 # host issue time vs drain, the multi-stream check
-timeout 900 python $R/bench.py --graph off --no-cpu-baseline --no-kernels --no-extras > $OUT/bench_eager.json 2>/dev/null
+timeout 900 python $R/bench.py --full --graph off --no-cpu-baseline --no-kernels --no-extras > $OUT/bench_eager.json 2>/dev/null
 timeout 900 python $R/tools/bwd_layers.py > $OUT/bwd_layers.txt 2>&1
 timeout 600 python $R/tools/warp_step_sweep.py 2>&1 | grep -v Warn > $OUT/warp_step_sweep.txt
 timeout 600 python $R/tools/rs_bwd1_cfg1.py 2>&1 | grep -v Warn > $OUT/rs_bwd1.txt
