@@ -882,9 +882,10 @@ rs_flow_irregular_kernel(const float* __restrict__ in2, int* __restrict__ count,
 // FIXED (round 5): the box holds 32-bit FIXED-POINT cells instead of doubles (ds_add_u32: half the LDS time of ds_add_f64 per
 // conflict-free instruction, a wave's lanes spread over twice as many banks, half the LDS -- see be_bwd_tile2_kernel).  The scale is
 // EXACT here: a block loads the grad_output values of its pixels for the four channels of a group before it adds anything, so the
-// group's maximum |g| is known (one unsigned maximum over the magnitude bits, reduced over the block); every contribution is
+// group's maximum |g| is known per channel (unsigned maxima over the magnitude bits, reduced over the block); every contribution is
 // w / sum x g with w / sum <= 1, at most one per pixel and cell, so 64 TH contributions of < 2^(31 - log2(64 TH)) cannot overflow.
-// One unit is <= max|g| / 2^21 (TH = 16).  A group with a NaN / Inf gradient takes the per-tap global-atomic path for its channels.
+// One unit is <= 2^-19 (TH = 16) of the channel's OWN maximum |g_c| over the block.  A group with a NaN / Inf gradient, or with a
+// channel whose maximum is below 2^-90, takes the per-tap global-atomic path for its channels.
 template <int HALF, int RPT, bool FIXED = false>
 __global__ void __launch_bounds__(kBlock)
 rs_bwd1_tile_kernel(const float* __restrict__ in2, const float* __restrict__ gout, float* __restrict__ gin1, int C, int Hi,
@@ -903,7 +904,7 @@ rs_bwd1_tile_kernel(const float* __restrict__ in2, const float* __restrict__ gou
     using AccT = typename std::conditional<FIXED, int, double>::type;
     AccT* box = reinterpret_cast<AccT*>(smem_raw);
     __shared__ int red[4][NW];
-    __shared__ unsigned redm[NW];
+    __shared__ unsigned redm[4][NW];
     __shared__ int flag;
 
     unsigned tid = xcd_remap(blockIdx.x, gridDim.x, remap);
@@ -1046,29 +1047,34 @@ rs_bwd1_tile_kernel(const float* __restrict__ in2, const float* __restrict__ gou
                 g[r][0] = buf_ld<float>(rg0, poffb[r]); g[r][1] = buf_ld<float>(rg1, poffb[r]);
                 g[r][2] = buf_ld<float>(rg2, poffb[r]); g[r][3] = buf_ld<float>(rg3, poffb[r]);
             }
-            float fx_inv = 1.f;
+            float fx_inv[4] = {1.f, 1.f, 1.f, 1.f};
             bool exact_path = false;
             if constexpr (FIXED) {
-                unsigned mb = 0;
+                // one scale PER CHANNEL: a channel's unit is 2^-kShift of its own maximum over the block, whatever its neighbours hold
+                unsigned mb[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
                 for (int r = 0; r < RPT; ++r)
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) mb = max(mb, __float_as_uint(g[r][q]) & 0x7FFFFFFFu);
-                mb = wave_max(mb);
-                if (lane == 0) redm[wave] = mb;
+                    for (int q = 0; q < 4; ++q) mb[q] = max(mb[q], __float_as_uint(g[r][q]) & 0x7FFFFFFFu);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    mb[q] = wave_max(mb[q]);
+                    if (lane == 0) redm[q][wave] = mb[q];
+                }
                 __syncthreads();                     // (also: the box is cleared)
 #pragma unroll
-                for (int k = 0; k < NW; ++k) mb = max(mb, redm[k]);
-                exact_path = mb >= 0x7F800000u;      // a NaN / Inf gradient in the group: its channels scatter per tap, exactly
-                int ex = 0;
-                (void)frexpf(__uint_as_float(mb), &ex);          // max|g| < 2^ex
-                const bool usable = mb != 0u && ex > -90 && !exact_path;
-                const float sc = usable ? ldexpf(1.f, kShift - ex) : 0.f;
-                fx_inv = usable ? ldexpf(1.f, ex - kShift) : 0.f;
+                for (int q = 0; q < 4; ++q) {
 #pragma unroll
-                for (int r = 0; r < RPT; ++r)
+                    for (int k = 0; k < NW; ++k) mb[q] = max(mb[q], redm[q][k]);
+                    int ex = 0;
+                    (void)frexpf(__uint_as_float(mb[q]), &ex);       // max|g_q| < 2^ex
+                    // a NaN / Inf gradient, or a channel too small for a float scale: the group's channels scatter per tap, exactly
+                    exact_path = exact_path || mb[q] >= 0x7F800000u || (mb[q] != 0u && ex <= -90);
+                    const float sc = mb[q] != 0u && ex > -90 ? ldexpf(1.f, kShift - ex) : 0.f;
+                    fx_inv[q] = sc != 0.f ? ldexpf(1.f, ex - kShift) : 0.f;
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) g[r][q] *= sc;          // (exact: a power of two; all zeros when there is nothing to add)
+                    for (int r = 0; r < RPT; ++r) g[r][q] *= sc;        // (exact: a power of two; all zeros when there is nothing to add)
+                }
             } else {
                 __syncthreads();
             }
@@ -1112,7 +1118,7 @@ rs_bwd1_tile_kernel(const float* __restrict__ in2, const float* __restrict__ gou
                 float* dst = dp + static_cast<size_t>(c - c0) * iplane + static_cast<size_t>(gy) * Wi + gx;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const float v = FIXED ? static_cast<float>(box[q * NCELL + i]) * fx_inv : static_cast<float>(box[q * NCELL + i]);
+                    const float v = FIXED ? static_cast<float>(box[q * NCELL + i]) * fx_inv[q] : static_cast<float>(box[q * NCELL + i]);
                     if (q < nch && v != 0.f && !(ablate & 2)) atomic_add(dst + static_cast<size_t>(q) * iplane, v);
                 }
             }
@@ -1217,13 +1223,20 @@ __device__ __attribute__((noinline)) RsFactors<HALF> rs_pixel_factors(float dx, 
         o.wx[f] = static_cast<float>(safe_div<float>(wxp[f], sx));
         o.wy[f] = static_cast<float>(safe_div<float>(wyp[f], sy));
     }
-    // every weight of an axis underflowed (sigma -> 0 away from the taps): SAFE_DIV's zero arm makes all products 0 -- the pixel adds
-    // nothing, and the "last = 1 - others" form must not invent a weight for it
-    o.degenerate = (sx == 0.f || sy == 0.f) ? 1 : 0;
+    // every one of the NT x NT weight PRODUCTS underflowed (sigma -> 0 away from the taps; the axis sums may still be positive): the
+    // reference's SAFE_DIV(wy wx, sum) is 0 for every tap -- the pixel adds nothing, as in rs_bwd1_far_kernel, and the "last = 1 -
+    // others" form must not invent a weight for it
+    o.degenerate = ((ablate & 8) ? (sx == 0.f || sy == 0.f) : (t.sum == 0.f)) ? 1 : 0;
     return o;
 }
 
 typedef float rs_f2 __attribute__((ext_vector_type(2)));
+
+// the biased exponent field of a magnitude |v| given as bits (255: NaN / Inf), 1 for a subnormal: 0 only for a zero.  A normal
+// |v| < 2^(rs_expo - 126).
+__device__ __forceinline__ unsigned rs_expo(unsigned a) {
+    return a >= 0x00800000u ? a >> 23 : (a != 0u ? 1u : 0u);
+}
 
 // Cells, round 6 second version.  A contribution is formed by ONE fused multiply-add, fma(w, g 2^s, 1.5 2^23): the sum is rounded to
 // the integer grid of the binade [2^23, 2^24) (round to nearest even, what v_cvt_i32_f32 did in a second instruction) and its BIT
@@ -1379,7 +1392,8 @@ rs_bwd1_owned_kernel(const float* __restrict__ in2, const float* __restrict__ go
     // true maximum + 1, tracks its own true maximum while it adds (the values pass through the registers anyway), and checks afterwards:
     // a maximum above the assumed range (a contribution left the magic-number binade: the box holds garbage) or more than 3 bits below it
     // (precision) clears the box and repeats the group with the exact exponent.  Neighbouring channels of a gradient rarely differ by
-    // 8 x; when they do the group costs twice, never correctness.
+    // 8 x; when they do the group costs twice, never correctness.  The maxima are kept PER CHANNEL (exponent fields): a group whose channels
+    // lie more than 2^3 apart has no exponent that resolves each of them to 2^(4 - bits) of its own maximum, and takes the exact path.
     unsigned mb = wave_max((ablate & 4) ? 0x3F800000u : lane_max(c0));
     if (lane == 0) redm[wave] = mb;
     __syncthreads();
@@ -1411,13 +1425,13 @@ rs_bwd1_owned_kernel(const float* __restrict__ in2, const float* __restrict__ go
             const int ex = __builtin_amdgcn_readfirstlane(min(max(ex_assumed, -80), 120));
             const float sc = ldexpf(1.f, bits - ex);
             fx_inv = ldexpf(1.f, ex - bits);
-            unsigned mt = 0;                            // this lane's true max|g| of the group
+            unsigned mq[4] = {0u, 0u, 0u, 0u};         // this lane's true max|g| (magnitude bits) per channel of the group
             float gn[4];
             load_row(0, gn);
 #pragma unroll
             for (int r = 0; r < PPT; ++r) {
 #pragma unroll
-                for (int q = 0; q < 4; ++q) mt = max(mt, __float_as_uint(gn[q]) & 0x7FFFFFFFu);
+                for (int q = 0; q < 4; ++q) mq[q] = max(mq[q], __float_as_uint(gn[q]) & 0x7FFFFFFFu);
                 const rs_f2 ga = {gn[0] * sc, gn[1] * sc}, gb = {gn[2] * sc, gn[3] * sc};       // (exact: a power of two)
                 if (r + 1 < PPT) load_row(r + 1, gn);
                 __builtin_amdgcn_sched_barrier(0);
@@ -1462,21 +1476,36 @@ rs_bwd1_owned_kernel(const float* __restrict__ in2, const float* __restrict__ go
                 }
                 __builtin_amdgcn_sched_barrier(0);      // one pixel at a time: interleaved, the eight unrolled steps want 237 registers
             }
-            mt = wave_max(mt);
-            if (lane == 0) redm[wave] = mt;
+            unsigned eq[4];                             // their exponent fields (rs_expo), maximum over the wave
+#pragma unroll
+            for (int q = 0; q < 4; ++q) eq[q] = wave_max(rs_expo(mq[q]));
+            if (lane == 0) redm[wave] = eq[0] | eq[1] << 8 | eq[2] << 16 | eq[3] << 24;
             __syncthreads();                            // every contribution of the attempt is in the box; the waves' maxima are out
 #pragma unroll
-            for (int k = 0; k < NW; ++k) mt = max(mt, redm[k]);
-            exact_path = mt >= 0x7F800000u;              // a NaN / Inf gradient among this group's pixels
-            int ex_true = ex;
-            if (mt != 0u && !exact_path) (void)frexpf(__uint_as_float(mt), &ex_true);       // max|g| < 2^ex_true
-            ex_true = __builtin_amdgcn_readfirstlane(ex_true);
-            const bool fits = ex_true <= ex && ex_true >= ex - 3 && ex_true > -80 && ex_true < 120;
-            usable = !exact_path && (mt == 0u || fits);
-            ex_assumed = mt != 0u && !exact_path ? ex_true + 1 : ex;       // the next group's assumption
+            for (int k = 0; k < NW; ++k)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) eq[q] = max(eq[q], (redm[k] >> (8 * q)) & 0xFFu);
+            unsigned emax = 0u, emin = 0xFFu;           // over the channels; emin over those that hold a non-zero gradient
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                emax = max(emax, eq[q]);
+                if (eq[q] != 0u) emin = min(emin, eq[q]);
+            }
+            emax = __builtin_amdgcn_readfirstlane(emax);
+            emin = __builtin_amdgcn_readfirstlane(emin);
+            exact_path = emax == 0xFFu;                  // a NaN / Inf gradient among this group's pixels
+            // max|g| < 2^ex_true (the biased exponent field less 126; frexpf's exponent), likewise ex_min for the smallest channel
+            const int ex_true = emax != 0u ? static_cast<int>(emax) - 126 : ex;
+            const int ex_min = emax != 0u ? static_cast<int>(emin) - 126 : ex;
+            // EVERY channel's maximum within 2^3 of the scale: one unit <= 2^(4 - bits) of the channel's own maximum over the block
+            const bool fits = ex_true <= ex && ex_min >= ex - 3 && ex_true > -80 && ex_true < 120;
+            usable = !exact_path && (emax == 0u || fits);
+            ex_assumed = emax != 0u && !exact_path ? ex_true + 1 : ex;       // the next group's assumption
             if (!usable && !exact_path && !(ablate & 4)) {
-                if (repeated) {
-                    exact_path = true;                  // (cannot happen: a repeat runs with the true exponent; defensive)
+                // no single exponent serves the group: channels more than 2^3 apart, or magnitudes outside the clamp of the scale
+                const bool hopeless = ex_min < ex_true - 3 || ex_true <= -80 || ex_true >= 120;
+                if (repeated || hopeless) {
+                    exact_path = true;                  // (a repeat runs with the true exponent: it fits unless hopeless; defensive)
                 } else {
                     // the SAME group again with the exact exponent: clear the four channel planes, do not advance c
                     repeated = true;
@@ -1524,19 +1553,12 @@ rs_bwd1_owned_kernel(const float* __restrict__ in2, const float* __restrict__ go
                 if (!rs_origin<HALF>(dx, dy, x, y, u0, v0)) continue;
                 RsTaps<float, HALF> t;
                 make_rs_taps<float, HALF>(t, dx, dy, sgm, x, y, Hi, Wi, 1, quirk != 0);
+                // the reference's weights SAFE_DIV(wy wx, sum), as rs_bwd1_far_kernel: a pixel whose products all underflowed adds 0 here too
                 float wxp[NT], wyp[NT];
-                float sx = 0.f, sy = 0.f;
 #pragma unroll
                 for (int f = 0; f < HALF; ++f) {
                     wxp[HALF - 1 - f] = t.wx[2 * f]; wxp[HALF + f] = t.wx[2 * f + 1];
                     wyp[HALF - 1 - f] = t.wy[2 * f]; wyp[HALF + f] = t.wy[2 * f + 1];
-                }
-#pragma unroll
-                for (int f = 0; f < NT; ++f) { sx += wxp[f]; sy += wyp[f]; }
-#pragma unroll
-                for (int f = 0; f < NT; ++f) {
-                    wxp[f] = static_cast<float>(safe_div<float>(wxp[f], sx));
-                    wyp[f] = static_cast<float>(safe_div<float>(wyp[f], sy));
                 }
                 float gq[4];
 #pragma unroll
@@ -1550,7 +1572,7 @@ rs_bwd1_owned_kernel(const float* __restrict__ in2, const float* __restrict__ go
                         float* dst = dp + static_cast<size_t>(c - c0) * iplane + static_cast<size_t>(Y0 + rr) * Wi + (X0 + cc);
 #pragma unroll
                         for (int q = 0; q < 4; ++q)
-                            if (q < nch) atomic_add(dst + static_cast<size_t>(q) * iplane, (wyp[pr] * wxp[pc]) * gq[q]);
+                            if (q < nch) atomic_add(dst + static_cast<size_t>(q) * iplane, static_cast<float>(safe_div<float>(wyp[pr] * wxp[pc], t.sum)) * gq[q]);
                     }
             }
         }

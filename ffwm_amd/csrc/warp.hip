@@ -1095,7 +1095,15 @@ warp_bwd_feat_tile_kernel(const float* __restrict__ flow, const float* __restric
 #pragma unroll
                     for (int c = 0; c < CG; ++c) fx_inv[c] = 0.f;
                 }
-                if (fits || exact_path || attempt == 1) break;
+                if (fits || exact_path) break;
+                if (attempt == 1) {
+                    // the true exponent did not fit either: a maximum outside the clamp of the scale (below 2^-80: the cells would resolve
+                    // a few units of it) -- the group's channels scatter per tap, exactly
+                    exact_path = true;
+#pragma unroll
+                    for (int c = 0; c < CG; ++c) fx_inv[c] = 0.f;
+                    break;
+                }
 #pragma unroll
                 for (int c = 0; c < CG; ++c) ex_assumed[c] = next_ex[c];
                 for (int i = threadIdx.x; i < CG * NC; i += kWtThreads) acc[i] = 0;
@@ -1361,7 +1369,15 @@ warp_bwd_feat_tile2_kernel(const float* __restrict__ flow, const float* __restri
 #pragma unroll
                 for (int c = 0; c < CG; ++c) fx_inv[c] = 0.f;
             }
-            if (fits || exact_path || attempt == 1) break;
+            if (fits || exact_path) break;
+            if (attempt == 1) {
+                // the true exponent did not fit either: a maximum outside the clamp of the scale (below 2^-80: the cells would resolve
+                // a few units of it) -- the group's channels scatter per tap, exactly
+                exact_path = true;
+#pragma unroll
+                for (int c = 0; c < CG; ++c) fx_inv[c] = 0.f;
+                break;
+            }
 #pragma unroll
             for (int c = 0; c < CG; ++c) ex_assumed[c] = next_ex[c];
             for (int i = threadIdx.x; i < CG * NC; i += kWtThreads) box[i] = 0;

@@ -259,6 +259,12 @@ def resample2d_backward(input1, input2, grad_output, kernel_size=2, dilation=1, 
     if tuple(grad_output.shape) != (B, C, H, W):
         raise ValueError("resample2d_backward: grad_output has the wrong shape")
     if grad_output.numel() == 0:
+        # nothing flows back, but what the caller handed over uninitialised must still come back as zeros: grad_input1[:B] in
+        # overwrite mode, grad_input2 always (it is written, never accumulated into)
+        if overwrite_input1 and grad_input1 is not None and B > 0 and grad_input1[:B].numel() > 0:
+            zero_fill(grad_input1[:B])
+        if grad_input2 is not None and grad_input2.numel() > 0:
+            zero_fill(grad_input2)
         return grad_input1, grad_input2
     flags = (1 if reference_quirk else 0) | (2 if overwrite_input1 else 0)
     with _on_device(input1) as stream:
@@ -305,6 +311,8 @@ def warp_backward(feat, flow, grad_output, flipcat=False, grad_feat=None, grad_f
     if tuple(grad_output.shape) != (B, 2 * C if flipcat else C, H, W):
         raise ValueError("warp_backward: grad_output has the wrong shape")
     if grad_output.numel() == 0:
+        if overwrite_feat and grad_feat is not None and grad_feat.numel() > 0:
+            zero_fill(grad_feat)                # the caller's buffer may be uninitialised: nothing flows back, so it is zero
         return grad_feat, grad_flow
     with _on_device(feat) as stream:
         _lib.check(_lib.load().ffwm_warp_backward(

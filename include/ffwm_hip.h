@@ -124,11 +124,23 @@ int ffwm_resample2d_forward(const void* input1, const void* input2, void* output
                             int kernel_size, int dilation, int dtype, void* stream);
 
 /* grad_input1[B,C,Hi,Wi] += scatter (resample2d_kernel.cu:98-202); grad_input2[B,3,H,W] is
- * OVERWRITTEN (resample2d_kernel.cu:204-330).  reference_quirk != 0 keeps the reference's
- * `alpha = xf - int(xf)` truncation in the grad_input1 weights (:137-138); 0 uses floor (the
- * true gradient).  reference_quirk bit 1 (value 2, ABI 5): grad_input1 arrives UNINITIALISED and is overwritten -- the
- * owned-tile kernels store every cell exactly once (no zero-fill by the caller, no atomics on the regular path), every
- * other path clears the buffer itself first.  Either gradient may be NULL. */
+ * OVERWRITTEN (resample2d_kernel.cu:204-330).  Either gradient may be NULL.
+ * reference_quirk is a word of two FLAGS:
+ *   bit 0 (value 1): the quirk -- keep the reference's `alpha = xf - int(xf)` truncation in the grad_input1 weights (:137-138);
+ *                    clear: floor (the true gradient).
+ *   bit 1 (value 2, ABI 5): overwrite -- grad_input1 arrives UNINITIALISED and is overwritten: the owned-tile kernels store every
+ *                    cell exactly once (no zero-fill by the caller, no atomics on the regular path), every other path clears the
+ *                    buffer itself first.  (With an empty grid nothing is launched: ffwm_amd.ops clears the buffer itself.)
+ * A pixel whose NT x NT weight products all underflow (the reference's 16-product sum is 0) adds nothing, on every path.
+ *
+ * Precision of the SCATTER outputs (grad_input1 here; grad_source of the block extractor and block attention, grad_feat of the warp):
+ * fp32 paths that accumulate in 32-bit fixed-point LDS cells scale a cell by a power of two taken from the largest gradient of its
+ * CHANNEL among the pixels of the block that owns it.  For a cell with contributions w_i g_i (w_i >= 0), at every finite cell
+ *     |got - ref| <= rho * sum_i |w_i g_i|  +  eta * L  (+ 1e-38),   rho = 2^-16, eta = 2^-12,
+ * with ref the exact sum and L the largest |g| of the same channel within reach of the cell (the block's pixel region: 64 x 48
+ * pixels for the resample2d owned tiles, 64 x 32 windows plus halo for the block extractor).  Non-finite cells sit exactly where
+ * the reference's float atomics put them.  A flow that CONTRACTS many pixels onto one cell scales eta with the counted population.
+ * (tests/scatter_bounds.py derives the two constants; the fp32 reference itself meets the bound with rho / 4 and eta = 0.) */
 int ffwm_resample2d_backward(const void* input1, const void* input2, const void* grad_output,
                              void* grad_input1, void* grad_input2, int64_t B, int64_t C,
                              int64_t Hi, int64_t Wi, int64_t H, int64_t W, int kernel_size,

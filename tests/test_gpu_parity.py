@@ -472,7 +472,8 @@ def test_block_extractor_backward_fixed_point_cells_tail_cases(oracle, kind, fix
             int((~torch.isfinite(got)).sum()), got.numel(), int((~fin).sum()))
         if fin.any():
             scale = 1e-30 + float(ref[fin].abs().max())
-            # relative to the LARGEST gradient: what a fixed-point cell resolves (and what float atomics in another order lose)
+            # relative to the LARGEST gradient: what a fixed-point cell resolves.  (Float atomics in another order lose far less: their
+            # error follows each cell's own terms.  The per-cell bound is in tests/test_gpu_scatter_bounds.py.)
             assert float((got[fin] - ref[fin]).abs().max()) <= 2e-5 * scale, (kind, float((got[fin] - ref[fin]).abs().max()) / scale)
 
 
