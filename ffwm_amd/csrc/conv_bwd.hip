@@ -421,7 +421,8 @@ extern "C" int ffwm_conv2d_wgrad(const void* rows, const void* gathered, void* g
     const float* x = static_cast<const float*>(gathered);
     float* dw = static_cast<float*>(grad_weight);
     if (kernel == 3) hipLaunchKernelGGL((conv_wgrad_generic_kernel<3, 3>), grid, dim3(kBlock), 0, st, a, x, dw, g);
-    else hipLaunchKernelGGL((conv_wgrad_generic_kernel<4, 4>), grid, dim3(kBlock), 0, st, a, x, dw, g);
+    else if (kernel == 4) hipLaunchKernelGGL((conv_wgrad_generic_kernel<4, 4>), grid, dim3(kBlock), 0, st, a, x, dw, g);
+    else hipLaunchKernelGGL((conv_wgrad_generic_kernel<1, 1>), grid, dim3(kBlock), 0, st, a, x, dw, g);      // 1x1: the entry accepts it; it used to decode its columns as 4x4 taps
     return check_launch(fn);
 }
 
