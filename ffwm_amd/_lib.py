@@ -115,16 +115,12 @@ def load():
     if got != ABI_VERSION:
         raise FFWMError("libffwm_hip.so ABI version %d, expected %d: rebuild it" % (got, ABI_VERSION))
     _lib = lib
-    # FFWM_OPTS="key=value,key=value": tuning / ablation switches (ffwm_set_option) from the environment, for experiments
+    # FFWM_OPTS="key=value,key=value": tuning switches (ffwm_set_option) from the environment, for experiments
     # with unmodified callers (bench.py, tools/)
     for kv in filter(None, os.environ.get("FFWM_OPTS", "").split(",")):
         k, _, v = kv.partition("=")
         if lib.ffwm_set_option(k.strip().encode(), int(v)) < 0:
-            raise FFWMError("FFWM_OPTS: unknown option %r" % k)
-        if k.strip() == "ablate" and int(v) != 0:
-            import warnings
-            warnings.warn("FFWM_OPTS: ablate=%s -- timing-only kernel variants are ON: forward / backward RESULTS ARE WRONG "
-                          "(bench experiments only)" % v)
+            raise FFWMError("FFWM_OPTS: unknown option %r (or a negative value)" % k)
     return lib
 
 
@@ -168,7 +164,8 @@ def prof_collect():
 
 
 def set_option(key, value):
+    """-> the previous value; FFWMError for a key the library does not know or a negative value."""
     rc = load().ffwm_set_option(key.encode(), int(value))
-    if rc < 0 and key not in ("be_fwd_variant", "be_bwd_variant", "channel_slab", "xcd_remap", "ablate", "rows_per_thread", "scatter_variant", "be_bwd_halo", "be_bwd_rows", "warp_fwd_variant"):
+    if rc < 0:
         check(rc, "ffwm_set_option")
     return rc

@@ -194,12 +194,11 @@ constexpr int kLdsCols = 128;
 // extractor + attention consumer; see the "block attention" section below):
 //   0  block_extractor: the samples are the output                      out [B, C, k Hf, k Wf]
 //   1  attention forward: out = (sum_ij s_ij * w_ij) / k^2              out [B, C, Hf, Wf], aux = w [B, k^2, Hf, Wf]
-//   2  attention weight gradient: gw_ij += sum_c s_ij * (g_c / k^2)     out = gw [B, k^2, Hf, Wf] (atomic), aux = g [B, C, Hf, Wf]
 template <typename T, int K, int RPT, int MODE = 0>
 __global__ void __launch_bounds__(kBlock)
 be_fwd_lds_kernel(const T* __restrict__ src, const T* __restrict__ flow, T* __restrict__ out, int C,
                   int Hs, int Ws, int Hf, int Wf, int tiles_x, int tiles_y, int cslabs, int cs,
-                  int remap, int ablate, int nt, const T* __restrict__ aux = nullptr) {
+                  int remap, int nt, const T* __restrict__ aux = nullptr) {
     constexpr int NW = kBlock / kWave;
     constexpr int LROWS = (RPT == 1) ? 16 : 32;
     constexpr unsigned E = sizeof(T);
@@ -282,11 +281,10 @@ be_fwd_lds_kernel(const T* __restrict__ src, const T* __restrict__ flow, T* __re
     const unsigned sbytes = static_cast<unsigned>(splane * E);
     const unsigned obytes = static_cast<unsigned>(oplane * E);
     const T* sp = src + (static_cast<size_t>(b) * C + c0) * splane;
-    T* op = MODE == 2 ? out + static_cast<size_t>(b) * K * K * fplane : out + (static_cast<size_t>(b) * C + c0) * oplane;
+    T* op = out + (static_cast<size_t>(b) * C + c0) * oplane;
     const unsigned orow = static_cast<unsigned>(W) * E;
-    // fused modes: per-pixel attention weights (1) / upstream gradient of the current channel (2)
+    // MODE 1: the per-pixel attention weights
     const T* wb = MODE == 1 ? aux + static_cast<size_t>(b) * K * K * fplane : nullptr;
-    const T* gb = MODE == 2 ? aux + (static_cast<size_t>(b) * C + c0) * fplane : nullptr;
     constexpr T kK2 = static_cast<T>(K * K);
 
     if (use_lds) {
@@ -300,8 +298,7 @@ be_fwd_lds_kernel(const T* __restrict__ src, const T* __restrict__ flow, T* __re
             for (int ci = 0; ci < CI; ++ci) {
                 const int r = wave + ri * NW, cc = lane + ci * kWave;
                 const int gy = min(max(vmin + r, 0), Hs - 1), gx = min(max(umin + cc, 0), Ws - 1);
-                goff[ri][ci] = (r < bh && cc < bw && !(ablate & 1))
-                                   ? (static_cast<unsigned>(gy) * Ws + gx) * E : 0xFFFFFFF0u;   // OOB reads 0
+                goff[ri][ci] = (r < bh && cc < bw) ? (static_cast<unsigned>(gy) * Ws + gx) * E : 0xFFFFFFF0u;   // OOB reads 0
             }
         T stage[RI][CI];
         auto fetch = [&](const T* plane) {
@@ -326,11 +323,10 @@ be_fwd_lds_kernel(const T* __restrict__ src, const T* __restrict__ flow, T* __re
             obase[r] = MODE == 0 ? (static_cast<unsigned>(yfs[r]) * K * W + static_cast<unsigned>(xf) * K) * E
                                  : (static_cast<unsigned>(yfs[r]) * Wf + static_cast<unsigned>(xf)) * E;
         }
-        if constexpr (MODE != 0) {
-            // Fused consumers: the k x k samples are linear in the (k+1)^2 neighbourhood cells n_ab, so
-            //   MODE 1  out = sum_ab coef_ab n_ab,  coef_ab = sum_ij (w_ij / k^2) [bilinear weight of cell ab in sample ij]
-            //           -- formed ONCE per pixel, then (k+1)^2 LDS reads + fmas per channel instead of 4 k^2 + k^2;
-            //   MODE 2  T_ab += (g_c / k^2) n_ab per channel, and gw_ij = sum_ab [weight of ab in ij] T_ab once at the end.
+        if constexpr (MODE == 1) {
+            // Fused consumer: the k x k samples are linear in the (k+1)^2 neighbourhood cells n_ab, so
+            //   out = sum_ab coef_ab n_ab,  coef_ab = sum_ij (w_ij / k^2) [bilinear weight of cell ab in sample ij]
+            // -- formed ONCE per pixel, then (k+1)^2 LDS reads + fmas per channel instead of 4 k^2 + k^2.
             // (Same sums as the composition, re-associated: ~1e-7 relative.)
             constexpr int NC = (K + 1) * (K + 1);
             T coef[RPT][NC];
@@ -338,28 +334,20 @@ be_fwd_lds_kernel(const T* __restrict__ src, const T* __restrict__ flow, T* __re
             for (int r = 0; r < RPT; ++r)
 #pragma unroll
                 for (int q = 0; q < NC; ++q) coef[r][q] = 0;
-            T gcur[RPT], gnxt[RPT];        // MODE 2: g / k^2 of the current / next channel
-#pragma unroll
-            for (int r = 0; r < RPT; ++r) gcur[r] = gnxt[r] = 0;
             const size_t pixr0 = static_cast<size_t>(xf);
-            if constexpr (MODE == 1) {
 #pragma unroll
-                for (int r = 0; r < RPT; ++r)
+            for (int r = 0; r < RPT; ++r)
 #pragma unroll
-                    for (int i = 0; i < K; ++i)
+                for (int i = 0; i < K; ++i)
 #pragma unroll
-                        for (int j = 0; j < K; ++j) {
-                            const T wij = wb[(i * K + j) * fplane + static_cast<size_t>(yfs[r]) * Wf + pixr0] / kK2;
-                            const T wt = wij * wyt[r][i], wbm = wij * wyb[r][i];
-                            coef[r][i * (K + 1) + j] = fma_t<T>(wt, wxl[r][j], coef[r][i * (K + 1) + j]);
-                            coef[r][i * (K + 1) + j + 1] = fma_t<T>(wt, wxr[r][j], coef[r][i * (K + 1) + j + 1]);
-                            coef[r][(i + 1) * (K + 1) + j] = fma_t<T>(wbm, wxl[r][j], coef[r][(i + 1) * (K + 1) + j]);
-                            coef[r][(i + 1) * (K + 1) + j + 1] = fma_t<T>(wbm, wxr[r][j], coef[r][(i + 1) * (K + 1) + j + 1]);
-                        }
-            } else {
-#pragma unroll
-                for (int r = 0; r < RPT; ++r) gcur[r] = gb[static_cast<size_t>(yfs[r]) * Wf + pixr0] / kK2;
-            }
+                    for (int j = 0; j < K; ++j) {
+                        const T wij = wb[(i * K + j) * fplane + static_cast<size_t>(yfs[r]) * Wf + pixr0] / kK2;
+                        const T wt = wij * wyt[r][i], wbm = wij * wyb[r][i];
+                        coef[r][i * (K + 1) + j] = fma_t<T>(wt, wxl[r][j], coef[r][i * (K + 1) + j]);
+                        coef[r][i * (K + 1) + j + 1] = fma_t<T>(wt, wxr[r][j], coef[r][i * (K + 1) + j + 1]);
+                        coef[r][(i + 1) * (K + 1) + j] = fma_t<T>(wbm, wxl[r][j], coef[r][(i + 1) * (K + 1) + j]);
+                        coef[r][(i + 1) * (K + 1) + j + 1] = fma_t<T>(wbm, wxr[r][j], coef[r][(i + 1) * (K + 1) + j + 1]);
+                    }
             // Two channels ahead: the box of channel c+2 is requested (into the register set that channel c
             // just left) before channel c is processed, so a fetch has two iterations to land -- one block
             // iteration is only ~(k+1)^2 fmas per pixel, far shorter than the memory latency.
@@ -386,85 +374,35 @@ be_fwd_lds_kernel(const T* __restrict__ src, const T* __restrict__ flow, T* __re
             // `hold` carries channel c+1 (in flight or landed), `spare` is free for channel c+2
             auto iteration = [&](int c, T (&hold)[RI][CI], T (&spare)[RI][CI]) {
                 const bool more = c + 1 < c1;
-                if constexpr (MODE == 2) {
-                    if (more) {
-#pragma unroll
-                        for (int r = 0; r < RPT; ++r)
-                            gnxt[r] = gb[static_cast<size_t>(c + 1 - c0) * fplane + static_cast<size_t>(yfs[r]) * Wf + pixr0] / kK2;
-                    }
-                }
                 if (c + 2 < c1) fetch_to(sp + static_cast<size_t>(c + 2 - c0) * splane, spare);
                 const rsrc_t ro = make_rsrc(op, obytes);
 #pragma unroll
                 for (int r = 0; r < RPT; ++r) {
                     const T* nb = tile[p] + lbase[r];
-                    if constexpr (MODE == 1) {
-                        T orow[K + 1];
+                    T orow[K + 1];
 #pragma unroll
-                        for (int a = 0; a <= K; ++a) {
-                            orow[a] = coef[r][a * (K + 1)] * nb[a * kLdsCols];
+                    for (int a = 0; a <= K; ++a) {
+                        orow[a] = coef[r][a * (K + 1)] * nb[a * kLdsCols];
 #pragma unroll
-                            for (int bq = 1; bq <= K; ++bq) orow[a] = fma_t<T>(coef[r][a * (K + 1) + bq], nb[a * kLdsCols + bq], orow[a]);
-                        }
-                        T o = orow[0];
-#pragma unroll
-                        for (int a = 1; a <= K; ++a) o += orow[a];
-                        if (inx && iny[r]) {
-                            ElemRow<T, 1> ov;
-                            ov.v[0] = o;
-                            buf_store_row<T, 1>(ro, obase[r], ov);
-                        }
-                    } else {
-#pragma unroll
-                        for (int a = 0; a <= K; ++a)
-#pragma unroll
-                            for (int bq = 0; bq <= K; ++bq)
-                                coef[r][a * (K + 1) + bq] = fma_t<T>(gcur[r], nb[a * kLdsCols + bq], coef[r][a * (K + 1) + bq]);
+                        for (int bq = 1; bq <= K; ++bq) orow[a] = fma_t<T>(coef[r][a * (K + 1) + bq], nb[a * kLdsCols + bq], orow[a]);
                     }
-                }
-                if constexpr (MODE == 2) {
+                    T o = orow[0];
 #pragma unroll
-                    for (int r = 0; r < RPT; ++r) gcur[r] = gnxt[r];
+                    for (int a = 1; a <= K; ++a) o += orow[a];
+                    if (inx && iny[r]) {
+                        ElemRow<T, 1> ov;
+                        ov.v[0] = o;
+                        buf_store_row<T, 1>(ro, obase[r], ov);
+                    }
                 }
                 if (more) commit_from(tile[p ^ 1], hold);
                 __syncthreads();
-                op += (MODE == 2 ? 0 : oplane);
+                op += oplane;
                 p ^= 1;
             };
             for (int c = c0; c < c1; c += 2) {
                 iteration(c, stage2, stage);
                 if (c + 1 < c1) iteration(c + 1, stage, stage2);
-            }
-            if constexpr (MODE == 2) {
-#pragma unroll
-                for (int r = 0; r < RPT; ++r)
-                    if (inx && iny[r]) {
-                        // the tap weights again, from the flow (L2): keeping 4 k RPT of them live across the
-                        // channel loop would cost a third of the register file
-                        const size_t pix = static_cast<size_t>(yfs[r]) * Wf + pixr0;
-                        T fx0 = fb[pix], fy0 = fb[fplane + pix];
-                        asm volatile("" : "+v"(fx0), "+v"(fy0));
-                        T xr[K], yb2[K];
-#pragma unroll
-                        for (int j = 0; j < K; ++j) {
-                            const T dx = (fx0 + static_cast<T>(j - K / 2)) + static_cast<T>(xf);
-                            const T dy = (fy0 + static_cast<T>(j - K / 2)) + static_cast<T>(yfs[r]);
-                            xr[j] = dx - floor_t(dx);
-                            yb2[j] = dy - floor_t(dy);
-                        }
-#pragma unroll
-                        for (int i = 0; i < K; ++i)
-#pragma unroll
-                            for (int j = 0; j < K; ++j) {
-                                const T* t0 = &coef[r][i * (K + 1) + j];
-                                const T xl = 1 - xr[j], yt2 = 1 - yb2[i];
-                                T v = (xl * yt2) * t0[0];
-                                v = fma_t<T>(xr[j] * yt2, t0[1], v);
-                                v = fma_t<T>(xl * yb2[i], t0[K + 1], v);
-                                v = fma_t<T>(xr[j] * yb2[i], t0[K + 2], v);
-                                atomic_add(op + (i * K + j) * fplane + pix, v);
-                            }
-                    }
             }
             return;
         }
@@ -505,10 +443,7 @@ be_fwd_lds_kernel(const T* __restrict__ src, const T* __restrict__ flow, T* __re
                         s = fma_t<T>(wxr[r][j] * yb[i], cur[j + 1], s);
                         row.v[j] = s;
                     }
-                    if (ablate & 2) {      // ablation: keep the values live, skip the store
-#pragma unroll
-                        for (int j = 0; j < K; ++j) asm volatile("" ::"v"(row.v[j]));
-                    } else if (inx && iny[r]) {
+                    if (inx && iny[r]) {
                         if (nt) buf_store_row_nt<T, K>(ro, obase[r] + i * orow, row);
                         else buf_store_row<T, K>(ro, obase[r] + i * orow, row);
                     }
@@ -527,8 +462,8 @@ be_fwd_lds_kernel(const T* __restrict__ src, const T* __restrict__ flow, T* __re
     // is enough) used to walk its slab channel by channel with a dependent load group per tap row -- a 340 us tail on a
     // 230 us launch for a smooth flow whose extrema sit next to integers.
     if (!inx) return;
-    constexpr int CB = MODE == 0 ? 4 : 2;          // (the attention modes sit at a register-count step: one more VGPR costs a wave)
-    for (int c = c0; c < c1; c += CB, sp += CB * splane, op += (MODE == 2 ? 0 : CB * oplane)) {
+    constexpr int CB = MODE == 0 ? 4 : 2;          // (the attention mode sits at a register-count step: one more VGPR costs a wave)
+    for (int c = c0; c < c1; c += CB, sp += CB * splane, op += CB * oplane) {
         const int nb = (c1 - c) < CB ? (c1 - c) : CB;
 #pragma unroll 1
         for (int r = 0; r < RPT; ++r) {
@@ -537,14 +472,9 @@ be_fwd_lds_kernel(const T* __restrict__ src, const T* __restrict__ flow, T* __re
             const size_t pix = static_cast<size_t>(yf) * Wf + xf;
             const T fx0 = fb[pix], fy0 = fb[fplane + pix];
             const unsigned ob = (static_cast<unsigned>(yf) * K * W + static_cast<unsigned>(xf) * K) * E;
-            T osum[CB], gd[CB];
+            T osum[CB];
 #pragma unroll
-            for (int q = 0; q < CB; ++q) {
-                osum[q] = 0;
-                gd[q] = 0;
-                if constexpr (MODE == 2)
-                    if (q < nb) gd[q] = gb[static_cast<size_t>(c - c0 + q) * fplane + pix] / kK2;
-            }
+            for (int q = 0; q < CB; ++q) osum[q] = 0;
             Tap1<T> tx1[K];
 #pragma unroll
             for (int j = 0; j < K; ++j) tx1[j] = make_tap<T>(fx0, j - K / 2, xf, Ws);
@@ -577,7 +507,6 @@ be_fwd_lds_kernel(const T* __restrict__ src, const T* __restrict__ flow, T* __re
                         s = fma_t<T>(tx1[j].whi * ty1.whi, v[q][j][3], s);
                         row.v[j] = s;
                         if constexpr (MODE == 1) osum[q] = add_rn(osum[q], mul_rn(s, wb[(i * K + j) * fplane + pix]));
-                        if constexpr (MODE == 2) atomic_add(op + (i * K + j) * fplane + pix, gd[q] * s);
                     }
                     if constexpr (MODE == 0)
                         buf_store_row<T, K>(make_rsrc(op + static_cast<size_t>(q) * oplane, obytes), ob + i * orow, row);
@@ -1150,9 +1079,6 @@ be_bwd_tile_kernel(const float* __restrict__ src, const float* __restrict__ flow
     }
 }
 
-// FUSED (block attention backward): gout is the gradient of the attention output, [B, C, Hf, Wf], and the
-// k x k grad_output window of a pixel is (g / k^2) * w_ij with the attention weights w [B, k^2, Hf, Wf]
-// (what avg_pool2d's and the product's backward hand to the extractor) -- formed in registers, never stored.
 // FIXED (round 5): the accumulator box holds 32-bit FIXED-POINT cells instead of doubles.  ds_add_u32 retires in half the LDS time of
 // ds_add_f64 (4.3 vs 8.6 clk per conflict-free wave instruction, tools/ubench/atomics.hip), a 4-byte cell spreads a wave's lanes over
 // twice as many banks, and the box is half the size (more resident blocks).  What makes it safe:
@@ -1174,16 +1100,12 @@ be_bwd_tile_kernel(const float* __restrict__ src, const float* __restrict__ flow
 //   * rounding: one unit = 2^-e <= thr / 2^(bits - 1), i.e. <= 1e-6 of the tile's largest gradient per contribution at 23 bits (the
 //     reference's own float atomics round each partial sum to 6e-8 of ITS magnitude -- the same order once a cell has a few
 //     contributions).
-template <int K, int RH, int H, bool FUSED = false, bool ABL = false, int FIXED = 0>          // FIXED: 0 double cells, 1 fixed-point, 2 fixed-point at 5 waves per SIMD
-__global__ void __launch_bounds__(kBlock, (RH == 32 && K <= 3 && H <= 4 ? (FIXED == 2 ? 5 : 4) : 2))
+template <int K, int RH, int H, bool FIXED = false>          // FIXED: fixed-point cells instead of double cells
+__global__ void __launch_bounds__(kBlock, (RH == 32 && K <= 3 && H <= 4 ? 4 : 2))
 be_bwd_tile2_kernel(const float* __restrict__ src, const float* __restrict__ flow, const float* __restrict__ gout,
                    float* __restrict__ gsrc, float* __restrict__ gflow, int C, int Hs, int Ws, int Hf, int Wf,
-                   int ntx, int nty, int cslabs, int cs, int remap, const float* __restrict__ attn = nullptr, int ablate_arg = 0,
-                   int flush_rmw = 0) {
+                   int ntx, int nty, int cslabs, int cs, int remap, int flush_rmw = 0) {
     using T = float;
-    // bench-only ablation (tools/be_bwd_ablate.py; profiles/r04_be_bwd_ablation.txt): 1 = no LDS atomics, 2 = no flush atomics,
-    // 4 = no d(flow) arithmetic.  A compile-time zero in the product instantiations.
-    const int ablate = ABL ? ablate_arg : 0;
     constexpr int RW = kTileRW, NW = kBlock / kWave, PPT = RH / NW;
     constexpr int TW = RW, TH = RH;                       // the block's flow pixels: no overlap with its neighbours
     constexpr int AP = RW + 2 * H, AH = RH + 2 * H;       // accumulator / source box = tile grown by H
@@ -1197,7 +1119,7 @@ be_bwd_tile2_kernel(const float* __restrict__ src, const float* __restrict__ flo
     // Compared with the owned-tile kernel no pixel is visited twice (x1.0 instead of x1.52 pixel visits),
     // at the price of ~1.4 coalesced global atomics per pixel and channel.
     // DOUBLE on purpose: ds_add_f64 ~9 clk per wave, ds_add_f32 ~190 on gfx950 (tools/ubench/atomics.hip).
-    using AccT = typename std::conditional<FIXED != 0, int, double>::type;          // (FIXED: int cells)
+    using AccT = typename std::conditional<FIXED, int, double>::type;          // (FIXED: int cells)
     __shared__ AccT A[NA];
     __shared__ float red[NW];                              // FIXED: the waves' sampled maxima of the current channel
     unsigned t = xcd_remap(blockIdx.x, gridDim.x, remap);
@@ -1219,7 +1141,7 @@ be_bwd_tile2_kernel(const float* __restrict__ src, const float* __restrict__ flo
     const int W = K * Wf;
     const size_t splane = static_cast<size_t>(Hs) * Ws;
     const size_t fplane = static_cast<size_t>(Hf) * Wf;
-    const size_t oplane = FUSED ? fplane : static_cast<size_t>(K) * Hf * W;
+    const size_t oplane = static_cast<size_t>(K) * Hf * W;
     const unsigned sbytes = static_cast<unsigned>(splane * E);
     const unsigned obytes = static_cast<unsigned>(oplane * E);
     const unsigned orow = static_cast<unsigned>(W) * E;
@@ -1227,8 +1149,6 @@ be_bwd_tile2_kernel(const float* __restrict__ src, const float* __restrict__ flo
     T* gp = gsrc + (static_cast<size_t>(b) * C + c0) * splane;
     const T* op = gout + (static_cast<size_t>(b) * C + c0) * oplane;
     const rsrc_t rfl = make_rsrc(flow + static_cast<size_t>(b) * 2 * fplane, static_cast<unsigned>(2 * fplane * E));
-    const rsrc_t ratt = make_rsrc(FUSED ? attn + static_cast<size_t>(b) * K * K * fplane : src,
-                                  FUSED ? static_cast<unsigned>(K * K * fplane * E) : 0u);
 
     // out-of-image accumulator cells fold onto the border cell they clamp to (block-uniform)
     const bool inside = ax0 <= Ws - 1 && ay0 <= Hs - 1;   // the box meets the image (else: be_bwd_far2_kernel's job)
@@ -1266,7 +1186,7 @@ be_bwd_tile2_kernel(const float* __restrict__ src, const float* __restrict__ flo
     // FIXED: the population bound (kernel head).  Every `fit` pixel of the tile adds 1 to the box cell of its neighbourhood origin; the
     // block maximum of those counts sizes the fixed-point scale of every channel.  Same `regular` / `fit` arithmetic as the hot loop.
     int fx_bits = 23;
-    if constexpr (FIXED != 0) {
+    if constexpr (FIXED) {
         __shared__ int cred[NW];
         if (inside && xin) {
 #pragma unroll 1
@@ -1314,34 +1234,25 @@ be_bwd_tile2_kernel(const float* __restrict__ src, const float* __restrict__ flo
     for (int r = 0; r < PPT; ++r) gxa[r] = gya[r] = 0;
     // FIXED: one grad_output window value per pixel of this lane's rows (the centre element), as loads in flight: sample_issue() requests
     // them for channel plane `opc`, sample_max() folds them -- called around the flush of the previous channel, which hides their latency
-    constexpr int SSTEP = 2;          // every second row of the tile: 1024 samples per tile and channel (FUSED holds two loads per sample)
-    T smp[FIXED != 0 ? PPT : 1], smw[(FIXED != 0 && FUSED) ? PPT : 1];
+    constexpr int SSTEP = 2;          // every second row of the tile: 1024 samples per tile and channel
+    T smp[FIXED ? PPT : 1];
     T m_pre = 0;
     auto sample_issue = [&](const T* opc) {
-        if constexpr (FIXED != 0) {
+        if constexpr (FIXED) {
             const rsrc_t rgs = make_rsrc(opc, obytes);
             const int xs = min(max(xf, 0), Wf - 1);
 #pragma unroll
             for (int r = 0; r < PPT; r += SSTEP) {
                 const int ys = min(max(y0 + wave + r * NW, 0), Hf - 1);
-                if constexpr (FUSED) {
-                    const unsigned fo = (static_cast<unsigned>(ys) * Wf + xs) * E;
-                    smp[r] = buf_ld<T>(rgs, fo);
-                    smw[r] = buf_ld<T>(ratt, fo + static_cast<unsigned>((K / 2 * K + K / 2) * fplane * E));
-                } else {
-                    smp[r] = buf_ld<T>(rgs, (static_cast<unsigned>(ys) * K * W + static_cast<unsigned>(xs) * K) * E + (K / 2) * orow + (K / 2) * E);
-                }
+                smp[r] = buf_ld<T>(rgs, (static_cast<unsigned>(ys) * K * W + static_cast<unsigned>(xs) * K) * E + (K / 2) * orow + (K / 2) * E);
             }
         }
     };
     auto sample_max = [&]() {
-        if constexpr (FIXED != 0) {
+        if constexpr (FIXED) {
             T m = 0;
 #pragma unroll
-            for (int r = 0; r < PPT; r += SSTEP) {
-                const T v = FUSED ? (smp[r] / static_cast<T>(K * K)) * smw[r] : smp[r];
-                m = fmaxf(m, fabsf(v));                     // (fmaxf drops a NaN sample: such a pixel is "big" below)
-            }
+            for (int r = 0; r < PPT; r += SSTEP) m = fmaxf(m, fabsf(smp[r]));          // (fmaxf drops a NaN sample: such a pixel is "big" below)
             m_pre = m;
         }
     };
@@ -1355,7 +1266,7 @@ be_bwd_tile2_kernel(const float* __restrict__ src, const float* __restrict__ flo
         // FIXED: this channel's scale (see the kernel's head) from one window value per pixel -- requested while the previous channel was
         // flushed (`m_pre`), reduced over the block here
         T thr = 0, fx_scale = 0, fx_inv = 0;
-        if constexpr (FIXED != 0) {
+        if constexpr (FIXED) {
             T m = wave_max(m_pre);
             if (lane == 0) red[wave] = m;
             __syncthreads();
@@ -1377,8 +1288,8 @@ be_bwd_tile2_kernel(const float* __restrict__ src, const float* __restrict__ flo
         // requested before row r is processed (their addresses do not depend on the flow), so the
         // ~300 instructions of one row cover the latency of the next one's loads
         struct PixLoad {
-            T fx, fy, gs;              // gs: FUSED only, the pixel's upstream gradient
-            ElemRow<T, K> g[K];        // grad_output window (FUSED: the attention weights until `cur` is formed)
+            T fx, fy;
+            ElemRow<T, K> g[K];        // grad_output window
         };
         const int xfc = min(max(xf, 0), Wf - 1);
         auto request = [&](int r, PixLoad& d) {
@@ -1387,21 +1298,9 @@ be_bwd_tile2_kernel(const float* __restrict__ src, const float* __restrict__ flo
             const unsigned fo = (static_cast<unsigned>(yfc) * Wf + xfc) * E;
             d.fx = buf_ld<T>(rfl, fo);
             d.fy = buf_ld<T>(rfl, fo + static_cast<unsigned>(fplane * E));
-            if constexpr (FUSED) {
-                ElemRow<T, 1> gv;
-                buf_load_row_nt<T, 1>(rg, fo, gv);
-                d.gs = gv.v[0];
+            const unsigned ob = (static_cast<unsigned>(yfc) * K * W + static_cast<unsigned>(xfc) * K) * E;
 #pragma unroll
-                for (int i = 0; i < K; ++i)
-#pragma unroll
-                    for (int j = 0; j < K; ++j)
-                        d.g[i].v[j] = buf_ld<T>(ratt, fo + static_cast<unsigned>((i * K + j) * fplane * E));   // L2-resident
-            } else {
-                d.gs = 0;
-                const unsigned ob = (static_cast<unsigned>(yfc) * K * W + static_cast<unsigned>(xfc) * K) * E;
-#pragma unroll
-                for (int i = 0; i < K; ++i) buf_load_row_nt<T, K>(rg, ob + i * orow, d.g[i]);   // read exactly once: streaming (nt) loads, -3 %
-            }
+            for (int i = 0; i < K; ++i) buf_load_row_nt<T, K>(rg, ob + i * orow, d.g[i]);   // read exactly once: streaming (nt) loads, -3 %
         };
         PixLoad nxt;
         request(0, nxt);
@@ -1411,13 +1310,6 @@ be_bwd_tile2_kernel(const float* __restrict__ src, const float* __restrict__ flo
             const int yf = y0 + row;
             PixLoad cur = nxt;
             if (r + 1 < PPT) request(r + 1, nxt);
-            if constexpr (FUSED) {
-                const T gd = cur.gs / static_cast<T>(K * K);
-#pragma unroll
-                for (int i = 0; i < K; ++i)
-#pragma unroll
-                    for (int j = 0; j < K; ++j) cur.g[i].v[j] = gd * cur.g[i].v[j];
-            }
             const bool row_owned = gflow != nullptr;
             T gx = 0, gy = 0;
             if (xin && yf >= 0 && yf < Hf) {
@@ -1448,7 +1340,7 @@ be_bwd_tile2_kernel(const float* __restrict__ src, const float* __restrict__ flo
                 const unsigned ob = (static_cast<unsigned>(yf) * K * W + static_cast<unsigned>(xf) * K) * E;
                 bool big = false;
                 T inv_pix = 1;
-                if constexpr (FIXED != 0) {
+                if constexpr (FIXED) {
                     // "big": a window value >= thr, a NaN or an Inf -- one unsigned maximum over the values' magnitude bits (for
                     // non-negative floats the bit patterns order like the values, NaN / Inf patterns lie above every finite one;
                     // thr == 0 makes every pixel big).  A small pixel's window is pre-scaled by 2^e (exact): the contributions come
@@ -1498,8 +1390,7 @@ be_bwd_tile2_kernel(const float* __restrict__ src, const float* __restrict__ flo
                             T v = 0;
                             if (r2 < K) v = tx[r2][c2] * yt[r2];
                             if (r2 > 0) v = (r2 < K) ? fma_t<T>(tx[r2 - 1][c2], wyb[r2 - 1], v) : tx[r2 - 1][c2] * wyb[r2 - 1];
-                            if (ablate & 1) { if (v == 12345.f) A[0] = 1; continue; }            // bench-only: no LDS atomics
-                            if constexpr (FIXED != 0) {
+                            if constexpr (FIXED) {
                                 // (a big pixel scatters below instead: the box never sees a value it cannot hold)
                                 if (!big)
                                     __hip_atomic_fetch_add(ap + r2 * AP + c2, __float2int_rn(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1509,7 +1400,7 @@ be_bwd_tile2_kernel(const float* __restrict__ src, const float* __restrict__ flo
                             }
                         }
                     }
-                    if constexpr (FIXED != 0) {
+                    if constexpr (FIXED) {
                         if (big) {
                             // the exact per-tap scatter of be_bwd_far2_kernel for this pixel and channel (rare: the sampled maximum
                             // missed this window by more than 4 x, or a non-finite gradient)
@@ -1539,7 +1430,7 @@ be_bwd_tile2_kernel(const float* __restrict__ src, const float* __restrict__ flo
                     // d(flow) (:163-164), only where this wave's row belongs to the tile (wave-uniform) and for
                     // the lanes that own their pixel: products regrouped into source differences, summed along
                     // the rows (gx) / columns (gy) of the window first
-                    if (row_owned && !(ablate & 4)) {
+                    if (row_owned) {
                         const T* nb = S + (owned ? sv * AP + su : 0);
                         T sp[K + 1], sc[K + 1];
 #pragma unroll
@@ -1560,7 +1451,7 @@ be_bwd_tile2_kernel(const float* __restrict__ src, const float* __restrict__ flo
 #pragma unroll
                             for (int j = 0; j <= K; ++j) sp[j] = sc[j];
                         }
-                        if constexpr (FIXED != 0) {
+                        if constexpr (FIXED) {
                             gx *= inv_pix;
                             gy *= inv_pix;
                         }
@@ -1575,10 +1466,7 @@ be_bwd_tile2_kernel(const float* __restrict__ src, const float* __restrict__ flo
 #pragma unroll 1
                         for (int j = 0; j < K; ++j) {
                             const Tap1<T> tx1 = make_tap<T>(fx0, j - K / 2, xf, Ws);
-                            const T gv = FUSED ? (cur.gs / static_cast<T>(K * K)) *
-                                                     buf_ld<T>(ratt, (static_cast<unsigned>(yf) * Wf + xf) * E +
-                                                                         static_cast<unsigned>((i * K + j) * fplane * E))
-                                               : buf_ld<T>(rg, ob + i * orow + j * E);
+                            const T gv = buf_ld<T>(rg, ob + i * orow + j * E);
                             const int cxs[2] = {static_cast<int>(tx1.lo), static_cast<int>(tx1.hi)};
                             const int cys[2] = {static_cast<int>(ty1.lo), static_cast<int>(ty1.hi)};
                             const T wxs[2] = {tx1.wlo, tx1.whi}, wys[2] = {ty1.wlo, ty1.whi};
@@ -1603,10 +1491,10 @@ be_bwd_tile2_kernel(const float* __restrict__ src, const float* __restrict__ flo
         // first (one thread per accumulator row), then rows (one thread per column)
         // (FIXED: the sums run in 64-bit -- a fold can collect a large part of the box -- and a total that does not fit the 32-bit cell
         // goes straight to the clamped cell of grad_source)
-        using FoldT = typename std::conditional<FIXED != 0, long long, double>::type;
+        using FoldT = typename std::conditional<FIXED, long long, double>::type;
         T* gfold = gp + static_cast<size_t>(c - c0) * splane;
         auto fold_into = [&](AccT& cell, FoldT s, int cy, int cx) {
-            if constexpr (FIXED != 0) {
+            if constexpr (FIXED) {
                 const long long t = static_cast<long long>(cell) + s;
                 if (t >= -2147483647LL && t <= 2147483647LL) {
                     cell = static_cast<int>(t);
@@ -1694,9 +1582,9 @@ be_bwd_tile2_kernel(const float* __restrict__ src, const float* __restrict__ flo
                         const bool interior = static_cast<unsigned>(acol - 2 * H) < static_cast<unsigned>(TW - 2 * H) &&
                                               static_cast<unsigned>(arow - 2 * H) < static_cast<unsigned>(TH - 2 * H);
                         const T nx = buf_ld<T>(rn, off * E);
-                        const T v = FIXED != 0 ? static_cast<T>(A[idx]) * fx_inv : static_cast<T>(A[idx]);
+                        const T v = FIXED ? static_cast<T>(A[idx]) * fx_inv : static_cast<T>(A[idx]);
                         A[idx] = 0;
-                        if (v != 0 && in_img && !(ablate & 2)) {
+                        if (v != 0 && in_img) {
                             if (interior) gplane[off] = old[q] + v;
                             else atomic_add(gplane + off, v);
                         }
@@ -1722,9 +1610,9 @@ be_bwd_tile2_kernel(const float* __restrict__ src, const float* __restrict__ flo
                 for (int q = 0; q < 4; ++q) {
                     const int idx = i0 + q * kBlock + tid;
                     if (idx < NA) {
-                        const T v = FIXED != 0 ? static_cast<T>(A[idx]) * fx_inv : static_cast<T>(A[idx]);
+                        const T v = FIXED ? static_cast<T>(A[idx]) * fx_inv : static_cast<T>(A[idx]);
                         A[idx] = 0;
-                        if (v != 0 && off[q] != 0xFFFFFFFFu && !(ablate & 2)) atomic_add(gplane + off[q], v);
+                        if (v != 0 && off[q] != 0xFFFFFFFFu) atomic_add(gplane + off[q], v);
                         if (more) S[idx] = st[q];
                     }
                 }
@@ -1945,19 +1833,16 @@ int launch_fwd(const T* src, const T* flow, T* out, int64_t B, int64_t C, int64_
                 hipLaunchKernelGGL((be_fwd_lds_kernel<float, (KK <= 4 ? KK : 1), 4>), dim3(gridl),  \
                                    dim3(kBlock), 0, st, (const float*)src, (const float*)flow,     \
                                    (float*)out, (int)C, (int)Hs, (int)Ws,                          \
-                                   (int)Hf, (int)Wf, g.tiles_x, tyl, g.cslabs, g.cs, remap,        \
-                                   options().ablate, nt);                                          \
+                                   (int)Hf, (int)Wf, g.tiles_x, tyl, g.cslabs, g.cs, remap, nt);   \
             else if (rpt >= 2)                                                                     \
                 hipLaunchKernelGGL((be_fwd_lds_kernel<float, (KK <= 4 ? KK : 1), 2>), dim3(gridl),  \
                                    dim3(kBlock), 0, st, (const float*)src, (const float*)flow,     \
                                    (float*)out, (int)C, (int)Hs, (int)Ws,                          \
-                                   (int)Hf, (int)Wf, g.tiles_x, tyl, g.cslabs, g.cs, remap,        \
-                                   options().ablate, nt);                                          \
+                                   (int)Hf, (int)Wf, g.tiles_x, tyl, g.cslabs, g.cs, remap, nt);   \
             else                                                                                   \
                 hipLaunchKernelGGL((be_fwd_lds_kernel<T, (KK <= 4 ? KK : 1), 1>), dim3(gridl),      \
                                    dim3(kBlock), 0, st, src, flow, out, (int)C, (int)Hs, (int)Ws,  \
-                                   (int)Hf, (int)Wf, g.tiles_x, tyl, g.cslabs, g.cs, remap,        \
-                                   options().ablate, nt);                                          \
+                                   (int)Hf, (int)Wf, g.tiles_x, tyl, g.cslabs, g.cs, remap, nt);   \
         } else                                                                                       \
             hipLaunchKernelGGL((be_fwd_kernel<T, KK>), dim3(g.grid), dim3(kBlock), 0, st, src,     \
                                flow, out, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, g.tiles_x,   \
@@ -2050,20 +1935,16 @@ int launch_bwd(const T* src, const T* flow, const T* gout, T* gsrc, T* gflow, in
     hipLaunchKernelGGL((KERNEL<KK, RR, HH>), dim3(grid), dim3(kBlock), 0, st, (const float*)src,              \
                        (const float*)flow, (const float*)gout, (float*)gsrc, (float*)gflow, (int)C, (int)Hs,  \
                        (int)Ws, (int)Hf, (int)Wf, ntx, nty, cslabs, cs, remap)
-#define FFWM_BE_TILE2(KK, RR, HH)                                                                             \
-    hipLaunchKernelGGL((be_bwd_tile2_kernel<KK, RR, HH>), dim3(grid), dim3(kBlock), 0, st, (const float*)src, \
+#define FFWM_BE_TILE2(KK, RR, HH, FIXED)                                                                      \
+    hipLaunchKernelGGL((be_bwd_tile2_kernel<KK, RR, HH, FIXED>), dim3(grid), dim3(kBlock), 0, st, (const float*)src, \
                        (const float*)flow, (const float*)gout, (float*)gsrc, (float*)gflow, (int)C, (int)Hs,  \
-                       (int)Ws, (int)Hf, (int)Wf, ntx, nty, cslabs, cs, remap, (const float*)nullptr, 0, flush_rmw)
-#define FFWM_BE_TILE2F(KK, RR, HH)                                                                            \
-    hipLaunchKernelGGL((be_bwd_tile2_kernel<KK, RR, HH, false, false, 1>), dim3(grid), dim3(kBlock), 0, st, (const float*)src, \
-                       (const float*)flow, (const float*)gout, (float*)gsrc, (float*)gflow, (int)C, (int)Hs,  \
-                       (int)Ws, (int)Hf, (int)Wf, ntx, nty, cslabs, cs, remap, (const float*)nullptr, 0, flush_rmw)
+                       (int)Ws, (int)Hf, (int)Wf, ntx, nty, cslabs, cs, remap, flush_rmw)
 #define FFWM_BE_TILE_K(KK)                                                                                    \
     case KK:                                                                                                  \
         if (shared_cells) {                                                                                   \
-            if (h == 8) FFWM_BE_TILE2(KK, 32, 8);                                                             \
-            else if (fixed_cells) FFWM_BE_TILE2F(KK, 32, 4);                                                  \
-            else FFWM_BE_TILE2(KK, 32, 4);                                                                    \
+            if (h == 8) FFWM_BE_TILE2(KK, 32, 8, false);                                                      \
+            else if (fixed_cells) FFWM_BE_TILE2(KK, 32, 4, true);                                             \
+            else FFWM_BE_TILE2(KK, 32, 4, false);                                                             \
         } else {                                                                                              \
             if (h == 8) FFWM_BE_TILE(be_bwd_tile_kernel, KK, 32, 8);                                          \
             else FFWM_BE_TILE(be_bwd_tile_kernel, KK, 32, 4);                                                 \
@@ -2071,20 +1952,10 @@ int launch_bwd(const T* src, const T* flow, const T* gout, T* gsrc, T* gflow, in
         break;
                 if (RH == 64) {
                     FFWM_BE_TILE(be_bwd_tile_kernel, 3, 64, 4);
-                } else if (shared_cells && k == 3 && h == 4 && options().ablate != 0) {
-                    if (fixed_cells)
-                        hipLaunchKernelGGL((be_bwd_tile2_kernel<3, 32, 4, false, true, 1>), dim3(grid), dim3(kBlock), 0, st, (const float*)src,
-                                           (const float*)flow, (const float*)gout, (float*)gsrc, (float*)gflow, (int)C, (int)Hs, (int)Ws, (int)Hf,
-                                           (int)Wf, ntx, nty, cslabs, cs, remap, (const float*)nullptr, options().ablate, flush_rmw);
-                    else
-                        hipLaunchKernelGGL((be_bwd_tile2_kernel<3, 32, 4, false, true, 0>), dim3(grid), dim3(kBlock), 0, st, (const float*)src,
-                                           (const float*)flow, (const float*)gout, (float*)gsrc, (float*)gflow, (int)C, (int)Hs, (int)Ws, (int)Hf,
-                                           (int)Wf, ntx, nty, cslabs, cs, remap, (const float*)nullptr, options().ablate, flush_rmw);
                 } else {
                     switch (k) { FFWM_BE_TILE_K(1) FFWM_BE_TILE_K(2) FFWM_BE_TILE_K(3) FFWM_BE_TILE_K(4) }
                 }
 #undef FFWM_BE_TILE_K
-#undef FFWM_BE_TILE2F
 #undef FFWM_BE_TILE2
 #undef FFWM_BE_TILE
             }
@@ -2139,8 +2010,7 @@ int check_dims(const char* fn, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int
 //   forward              ba_fwd_pix_kernel: coefficients Wy^T (w / k^2) Wx per pixel, boxes channel-innermost, one ds_read_b128 per cell
 //   d(source)            be_bwd_far2_kernel<.., FUSED> (pixels outside their box) + ba_bwd_src_kernel
 //   d(flow), d(weights)  ba_bwd_pix_kernel
-// Rounds 3-5's kernels: be_fwd_lds_kernel<.., MODE 1> is still the forward behind option ba_fwd_pix = 0; be_bwd_tile2_kernel<.., FUSED> and
-// be_fwd_lds_kernel<.., MODE 2> (d(source) + d(flow); d(weights)) are no longer instantiated -- the branches stay in the templates.
+// be_fwd_lds_kernel<.., MODE 1> (rounds 3-5) is still the forward behind option ba_fwd_pix = 0.
 // Everything else (float64, k != 3) runs the literal per-pixel kernels below.
 template <typename T>
 __global__ void __launch_bounds__(kBlock)
@@ -2227,9 +2097,9 @@ ba_bwd_generic(const T* __restrict__ src, const T* __restrict__ flow, const T* _
 }
 
 // ------------------------------------------------------------------------------ block attention backward by linearity (round 6)
-// be_bwd_tile2_kernel<.., FUSED> + be_fwd_lds_kernel<.., MODE 2> spend ~350 VALU instructions per (pixel, channel) -- VALU-bound at 0.12 of
-// the HBM roofline -- although the k x k window of the fused operator is (g_c / k^2) w_ij with a channel-INDEPENDENT w.  By linearity
-// everything channel-independent moves out of the channel loop:
+// Running the extractor's backward on the window (g_c / k^2) w_ij, formed per pixel AND channel, costs ~350 VALU instructions per (pixel,
+// channel) -- VALU-bound at 0.12 of the HBM roofline (rounds 4-5) -- although w is channel-INDEPENDENT.  By linearity everything
+// channel-independent moves out of the channel loop:
 //   * d(flow), d(weights) (ba_bwd_pix_kernel): with  P = sum_c (g_c / k^2) S_c  over the (K+1)^2 source neighbourhood of a pixel -- 16 LDS
 //     reads + 16 fmas per channel --   d(w_ij) = bilinear_ij(P),   d(flow_x) = sum_ij w_ij d/dx bilinear_ij(P),   d(flow_y) likewise, once
 //     per pixel and channel slab (11 global atomics).  A block keeps P of its 64 x TH pixels in registers while it walks its slab of
@@ -2242,7 +2112,7 @@ ba_bwd_generic(const T* __restrict__ src, const T* __restrict__ flow, const T* _
 //     population bound is counted as in be_bwd_tile2_kernel.  A channel whose maximum is not finite (NaN / Inf gradient or weight) or
 //     zero takes the per-tap global atomics of the reference for every pixel of the block.
 // Pixels that do not fit the box (flow wider than the halo, a floor that disagrees between taps, NaN flow): d(source) by
-// be_bwd_far2_kernel<.., FUSED> as before, d(flow) / d(weights) in ba_bwd_pix_kernel from global loads, tap by tap.
+// be_bwd_far2_kernel<.., FUSED>, d(flow) / d(weights) in ba_bwd_pix_kernel from global loads, tap by tap.
 // (First cut, one kernel for all three with P per slab of 4 channels: 594 us -- 216 of them the 11 atomics per pixel and 4-channel slab,
 // 144 the flush atomics; tools/r06/ba_bwd_time.py, profiles/r06_ba_bwd_linearity.txt.)
 struct BaTaps {
@@ -2275,9 +2145,6 @@ __device__ __forceinline__ BaTaps ba_taps(float fx0, float fy0, int xf, int yf, 
     return t;
 }
 
-#ifndef FFWM_BA_ABLATE
-#define FFWM_BA_ABLATE 0      // bench-only (tools/r06/ba_bwd_time.py): 1 no LDS atomics, 2 no flush atomics (ba_bwd_src_kernel); 4 no d(flow) / d(weights) atomics, 8 no P accumulation (ba_bwd_pix_kernel)
-#endif
 template <int TH, int NT, int CS>
 __global__ void __launch_bounds__(NT, 4)
 ba_bwd_src_kernel(const float* __restrict__ flow, const float* __restrict__ attn, const float* __restrict__ gout, float* __restrict__ gsrc,
@@ -2308,7 +2175,6 @@ ba_bwd_src_kernel(const float* __restrict__ flow, const float* __restrict__ attn
     const int nc = (c0 + CS < C) ? CS : C - c0;
     const size_t splane = static_cast<size_t>(Hs) * Ws;
     const size_t fplane = static_cast<size_t>(Hf) * Wf;
-    const unsigned sbytes = static_cast<unsigned>(splane * E);
     const unsigned fpb = static_cast<unsigned>(fplane * E);
     T* gp = gsrc + (static_cast<size_t>(b) * C + c0) * splane;
     const rsrc_t rfl = make_rsrc(flow + static_cast<size_t>(b) * 2 * fplane, 2 * fpb);
@@ -2452,7 +2318,7 @@ ba_bwd_src_kernel(const float* __restrict__ flow, const float* __restrict__ attn
                 if (!exact[c]) {
                     const T gs = (cur.g[c] * kInvKK) * fx_scale[c];
 #pragma unroll
-                    for (int q = 0; q < ((FFWM_BA_ABLATE & 1) ? 1 : (K + 1) * (K + 1)); ++q)
+                    for (int q = 0; q < (K + 1) * (K + 1); ++q)
                         __hip_atomic_fetch_add(ap + c * NA + (q / (K + 1)) * AP + (q % (K + 1)), __float2int_rn(gs * Kc[q]), __ATOMIC_RELAXED,
                                                __HIP_MEMORY_SCOPE_WORKGROUP);
                 } else {
@@ -2567,14 +2433,14 @@ ba_bwd_src_kernel(const float* __restrict__ flow, const float* __restrict__ attn
                 const int cy = ay0 + arow;
                 if (cy < 0 || cy >= Hs) continue;
                 const int a = A[c * NA + arow * AP + lane];
-                if (a != 0 && cxin && !(FFWM_BA_ABLATE & 2)) atomic_add(gplane + static_cast<size_t>(cy) * Ws + cxl, static_cast<T>(a) * iv);
+                if (a != 0 && cxin) atomic_add(gplane + static_cast<size_t>(cy) * Ws + cxl, static_cast<T>(a) * iv);
             }
 #pragma unroll 1
             for (int e = tid; e < AH * 2 * H; e += NT) {
                 const int arow = e / (2 * H), acol = RW + (e & (2 * H - 1));
                 const int cx = ax0 + acol, cy = ay0 + arow;
                 const int a = A[c * NA + arow * AP + acol];
-                if (a != 0 && cx >= 0 && cx < Ws && cy >= 0 && cy < Hs && !(FFWM_BA_ABLATE & 2))
+                if (a != 0 && cx >= 0 && cx < Ws && cy >= 0 && cy < Hs)
                     atomic_add(gplane + static_cast<size_t>(cy) * Ws + cx, static_cast<T>(a) * iv);
             }
         }
@@ -2736,12 +2602,11 @@ ba_bwd_pix_kernel(const float* __restrict__ src, const float* __restrict__ flow,
             const T* nb = S + nbo[r] * CG;
             T gd[CG];
 #pragma unroll
-            for (int c = 0; c < CG; ++c) gd[c] = ((FFWM_BA_ABLATE & 8) && c > 0) ? 0.f : g[r][c] * kInvKK;
+            for (int c = 0; c < CG; ++c) gd[c] = g[r][c] * kInvKK;
 #pragma unroll
             for (int q = 0; q < NP; ++q) {
 #pragma unroll
                 for (int h4 = 0; h4 < CG / 4; ++h4) {
-                    if ((FFWM_BA_ABLATE & 8) && (q & 3)) continue;
                     const f32x4 v = *reinterpret_cast<const f32x4*>(nb + ((q / (K + 1)) * AP + (q % (K + 1))) * CG + h4 * 4);
 #pragma unroll
                     for (int c = 0; c < 4; ++c) P[r][q] = fma_t<T>(gd[h4 * 4 + c], v[c], P[r][q]);
@@ -2780,14 +2645,14 @@ ba_bwd_pix_kernel(const float* __restrict__ src, const float* __restrict__ flow,
                     const T lef = fma_t<T>(tp.wyb[i], BL, yt[i] * TL), rig = fma_t<T>(tp.wyb[i], BR, yt[i] * TR);
                     gy = fma_t<T>(w[i * K + j], bot - top, gy);
                     gx = fma_t<T>(w[i * K + j], rig - lef, gx);
-                    if (gwp && !(FFWM_BA_ABLATE & 4)) atomic_add_off(gwp, fo[r] + static_cast<unsigned>(i * K + j) * fpb, fma_t<T>(tp.wyb[i], bot, yt[i] * top));
+                    if (gwp) atomic_add_off(gwp, fo[r] + static_cast<unsigned>(i * K + j) * fpb, fma_t<T>(tp.wyb[i], bot, yt[i] * top));
                 }
             }
         } else {
             // every tap on its own from global memory, like the reference (rare; a called function: its registers are not the hot path's)
             ba_pixel_by_taps(sp, rga, ratt, gw ? gw + static_cast<size_t>(b) * K * K * fplane : nullptr, nc, Hs, Ws, splane, fpb, fx0, fy0, xf, yf, pix, gx, gy);
         }
-        if (gflow && !(FFWM_BA_ABLATE & 4)) {
+        if (gflow) {
             atomic_add_off(gflow + static_cast<size_t>(b) * 2 * fplane, fo[r], gx);
             atomic_add_off(gflow + static_cast<size_t>(b) * 2 * fplane, fo[r] + fpb, gy);
         }
@@ -3018,10 +2883,10 @@ int launch_attn_fwd(const T* src, const T* flow, const T* wts, T* out, int64_t B
             LaunchScope ls("block_attention_fwd_lds", st, bytes);
             if (rpt == 4)
                 hipLaunchKernelGGL((be_fwd_lds_kernel<float, 3, 4, 1>), dim3(gridl), dim3(kBlock), 0, st, src, flow, out, (int)C,
-                                   (int)Hs, (int)Ws, (int)Hf, (int)Wf, g.tiles_x, tyl, g.cslabs, g.cs, options().xcd_remap, 0, 0, wts);
+                                   (int)Hs, (int)Ws, (int)Hf, (int)Wf, g.tiles_x, tyl, g.cslabs, g.cs, options().xcd_remap, 0, wts);
             else
                 hipLaunchKernelGGL((be_fwd_lds_kernel<float, 3, 1, 1>), dim3(gridl), dim3(kBlock), 0, st, src, flow, out, (int)C,
-                                   (int)Hs, (int)Ws, (int)Hf, (int)Wf, g.tiles_x, tyl, g.cslabs, g.cs, options().xcd_remap, 0, 0, wts);
+                                   (int)Hs, (int)Ws, (int)Hf, (int)Wf, g.tiles_x, tyl, g.cslabs, g.cs, options().xcd_remap, 0, wts);
             return check_launch("ffwm_block_attention_forward");
         }
     }
@@ -3038,8 +2903,6 @@ int launch_attn_bwd(const T* src, const T* flow, const T* wts, const T* gout, T*
                     int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, int k, hipStream_t st) {
     const double bytes = sizeof(T) * static_cast<double>(B) * (static_cast<double>(C) * Hf * Wf + 2.0 * C * Hs * Ws + (4.0 + k * k) * Hf * Wf);
     if constexpr (sizeof(T) == 4) {
-        // (rounds 4-5's route -- be_bwd_tile2_kernel<.., FUSED> + be_fwd_lds_kernel<.., MODE 2> -- is gone: 1.5 x slower, and round 6's wide-flow
-        // test found its d(weights) launch wrong where flows leave the forward kernel's LDS window)
         if (k == 3 && options().be_bwd_variant != 9 && Hs * Ws < (1LL << 29)) {
             const int mode = options().ba_bwd_fused;
             const int th = mode == 2 ? 16 : 32;

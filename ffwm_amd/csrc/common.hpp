@@ -29,6 +29,8 @@ int device_cus();
 int zero_fill(void* p, size_t bytes, hipStream_t st);
 constexpr int kMaxLdsBytes = 160 * 1024;
 
+// Tuning switches of ffwm_set_option.  Every value is >= 0 (0 = "auto" or "off"): ffwm_set_option refuses a negative one, so that its
+// return value -- the previous value -- is never mistaken for an error status.
 struct Options {
     int be_fwd_variant = 0;   // 0 = auto
     int be_bwd_variant = 0;
@@ -70,8 +72,6 @@ struct Options {
     int be_bwd_flush = 0;        // block_extractor / block attention shared-cell backward: 0 = every in-image cell by a global atomic, 1 = interior box cells by read-modify-write (round 6 experiment, slower)
     int zero_fill_memset = 0;    // 1 = zero_fill() calls hipMemsetAsync as rounds 1-4 did (diagnosis: reproduces the corrupted memset nodes)
     int conv_wgrad_unsliced = 0; // conv_bwd.hip tiled weight gradient: 1 = never cut the pixel range into slices (no zero-fill, no atomics: a diagnosis switch)
-    int conv_wgrad_prezeroed = 0; // conv_bwd.hip tiled weight gradient: 1 = the caller hands over ZEROED grad_weight / grad_bias (a slice of the trainer's gradient arena, cleared by one launch per step): a sliced launch skips its own zero-fill
-    int ablate = 0;           // bench-only ablation bits (1 = skip source fetch, 2 = skip stores)
 };
 Options& options();
 

@@ -200,7 +200,6 @@ __device__ __forceinline__ void winograd_epilogue(const f32x16 (&acc)[8], f32x4*
     }
 }
 
-template <int ABL>          // ABL: timing experiments only (bit 0 no patch loads, 1 no U loads, 2 no LDS commits, 3 no operand reads; raw variant: 4 no output stores, 5 no epilogue)
 __global__ void __launch_bounds__(kWinoThreads)
 winograd_conv_kernel(const float* __restrict__ x, const float* __restrict__ U, const float* __restrict__ bias, float* __restrict__ out,
                      const WinoGeo g, int remap) {
@@ -241,22 +240,19 @@ winograd_conv_kernel(const float* __restrict__ x, const float* __restrict__ U, c
     float d[16] = {};
     u32x4 uw[4] = {};
     auto fetch_slice = [&](int ch, int s) {          // U rows 2s, 2s + 1; patch elements 8 s ..+8
-        if (!(ABL & 2))
 #pragma unroll
-            for (int i = 2 * s; i < 2 * s + 2; ++i)
-                uw[i] = __builtin_amdgcn_raw_buffer_load_b128(ru, u_base + static_cast<unsigned>(ch) * (kWinoChunk * 4u) + i * 8192u, 0, 0);
+        for (int i = 2 * s; i < 2 * s + 2; ++i)
+            uw[i] = __builtin_amdgcn_raw_buffer_load_b128(ru, u_base + static_cast<unsigned>(ch) * (kWinoChunk * 4u) + i * 8192u, 0, 0);
         const int c = ch * 8 + 4 * sh + c_lo;
         const unsigned co = static_cast<unsigned>(c) * static_cast<unsigned>(HW) * 4u;
         const bool cin = c < g.C;                    // the channel tail and every chunk past the last read 0
-        if (!(ABL & 1))
 #pragma unroll
-            for (int q = 8 * s; q < 8 * s + 8; ++q) {
-                const unsigned o = poff[q] + co;
-                d[q] = buf_ld<float>(rx, (cin & (poff[q] != kOobOff)) ? o : kOobOff);
-            }
+        for (int q = 8 * s; q < 8 * s + 8; ++q) {
+            const unsigned o = poff[q] + co;
+            d[q] = buf_ld<float>(rx, (cin & (poff[q] != kOobOff)) ? o : kOobOff);
+        }
     };
     auto commit_slice = [&](f32x4* Ub, f32x4* Vb, int s) {   // U rows 2s, 2s + 1; V rows 2s, 2s + 1
-        if (ABL & 4) return;
 #pragma unroll
         for (int i = 2 * s; i < 2 * s + 2; ++i) reinterpret_cast<u32x4*>(Ub)[threadIdx.x + kWinoThreads * i] = uw[i];
         float* dst = reinterpret_cast<float*>(Vb) + (sh * 64 + ts) * 4 + c_lo;
@@ -290,7 +286,7 @@ winograd_conv_kernel(const float* __restrict__ x, const float* __restrict__ U, c
 #pragma unroll
         for (int grp = 0; grp < 4; ++grp) {
             const int cur = grp & 1, nxt = cur ^ 1;
-            if (grp < 3 && !(ABL & 8)) {
+            if (grp < 3) {
                 oa[nxt][0] = ap[(2 * grp + 2) * 128]; ob[nxt][0] = bp[(2 * grp + 2) * 128];
                 oa[nxt][1] = ap[(2 * grp + 3) * 128]; ob[nxt][1] = bp[(2 * grp + 3) * 128];
             }
@@ -343,7 +339,7 @@ constexpr int kWinoRawFloats = 8 * 4 * 128;      // 8 channels x (2 R + 2) rows 
 // SPLIT: the variant for calls with few pairs (WinoGeo::CS > 1).  A template parameter on purpose: the kernel lives on exactly 256
 // registers, and the split's extra state (a chunk origin per load cursor) as run-time values pushed three more registers to
 // scratch in the hot loop of EVERY call (measured: 146 -> 165 us per launch over the train step's layers).
-template <int ABL, bool SPLIT = false>
+template <bool SPLIT = false>
 __global__ void __launch_bounds__(kWinoThreads)
 winograd_conv_raw_kernel(const float* __restrict__ x, const float* __restrict__ U, const float* __restrict__ bias, float* __restrict__ out,
                          const WinoGeo g, int remap, int split_n, int split_chunks) {
@@ -465,27 +461,22 @@ winograd_conv_raw_kernel(const float* __restrict__ x, const float* __restrict__ 
     u32x4 uw[4] = {};
     float d[16] = {};
     auto load_raw = [&](u32x4 (&q)[2]) {             // L: the cursor's chunk, then the cursor moves on
-        if (!(ABL & 1)) {
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const bool cin = (first_chunk(cr.pair) + cr.ch) * 8 + qc[i] < g.C;
-                q[i] = __builtin_amdgcn_raw_buffer_load_b128(rx, (cin & (cr.qoff[i] != kOobOff)) ? cr.qoff[i] + static_cast<unsigned>(cr.ch) * (32u * HW) : kOobOff, 0, 0);
-            }
+        for (int i = 0; i < 2; ++i) {
+            const bool cin = (first_chunk(cr.pair) + cr.ch) * 8 + qc[i] < g.C;
+            q[i] = __builtin_amdgcn_raw_buffer_load_b128(rx, (cin & (cr.qoff[i] != kOobOff)) ? cr.qoff[i] + static_cast<unsigned>(cr.ch) * (32u * HW) : kOobOff, 0, 0);
         }
         advance(cr);
     };
     auto write_raw = [&](float* raw, const u32x4 (&q)[2]) {      // W: registers -> raw window
-        if (ABL & (4 | 256)) return;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
             if (qlds[i] >= 0) *reinterpret_cast<u32x4*>(raw + qlds[i]) = q[i];
     };
     auto load_u = [&](u32x4 (&u)[4], int s) {        // U rows 2s, 2s + 1 of the cursor's chunk; the cursor moves on after s = 1
-        if (!(ABL & 2)) {
 #pragma unroll
-            for (int i = 2 * s; i < 2 * s + 2; ++i)
-                u[i] = __builtin_amdgcn_raw_buffer_load_b128(ru, (cu.u_base != kOobOff && cu.ch < CHn) ? cu.u_base + static_cast<unsigned>(cu.ch) * (kWinoChunk * 4u) + i * 8192u : kOobOff, 0, 0);
-        }
+        for (int i = 2 * s; i < 2 * s + 2; ++i)
+            u[i] = __builtin_amdgcn_raw_buffer_load_b128(ru, (cu.u_base != kOobOff && cu.ch < CHn) ? cu.u_base + static_cast<unsigned>(cu.ch) * (kWinoChunk * 4u) + i * 8192u : kOobOff, 0, 0);
         if (s == 1) advance(cu);
     };
     auto read_patch = [&](const float* raw) {        // 3 reads per row: columns 2tx - 1 | 2tx, 2tx + 1 | 2tx + 2
@@ -501,11 +492,8 @@ winograd_conv_raw_kernel(const float* __restrict__ x, const float* __restrict__ 
         }
     };
     auto commit_slice = [&](f32x4* Ub, f32x4* Vb, const u32x4 (&u)[4], int s) {   // U rows 2s, 2s + 1; V rows 2s, 2s + 1
-        if (ABL & 4) return;
-        if (!(ABL & 64))
 #pragma unroll
-            for (int i = 2 * s; i < 2 * s + 2; ++i) reinterpret_cast<u32x4*>(Ub)[threadIdx.x + kWinoThreads * i] = u[i];
-        if (ABL & 128) return;
+        for (int i = 2 * s; i < 2 * s + 2; ++i) reinterpret_cast<u32x4*>(Ub)[threadIdx.x + kWinoThreads * i] = u[i];
         if (s == 0) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -555,15 +543,13 @@ winograd_conv_raw_kernel(const float* __restrict__ x, const float* __restrict__ 
 #pragma unroll
         for (int grp = 0; grp < 4; ++grp) {
             const int cur = grp & 1, nxt = cur ^ 1;
-            if (!(ABL & 8)) {
-                if (grp < 3) {
-                    oa[nxt][0] = ap[(2 * grp + 2) * 128]; ob[nxt][0] = bp[(2 * grp + 2) * 128];
-                    oa[nxt][1] = ap[(2 * grp + 3) * 128]; ob[nxt][1] = bp[(2 * grp + 3) * 128];
-                } else {                 // behind the barrier: the next step's first operands, from the buffers committed in groups 0, 1
-                    const f32x4* an = Un + oidx + wm * 32;
-                    const f32x4* bn = Vn + oidx + wn * 32;
-                    oa[nxt][0] = an[0]; ob[nxt][0] = bn[0]; oa[nxt][1] = an[128]; ob[nxt][1] = bn[128];
-                }
+            if (grp < 3) {
+                oa[nxt][0] = ap[(2 * grp + 2) * 128]; ob[nxt][0] = bp[(2 * grp + 2) * 128];
+                oa[nxt][1] = ap[(2 * grp + 3) * 128]; ob[nxt][1] = bp[(2 * grp + 3) * 128];
+            } else {                 // behind the barrier: the next step's first operands, from the buffers committed in groups 0, 1
+                const f32x4* an = Un + oidx + wm * 32;
+                const f32x4* bn = Vn + oidx + wn * 32;
+                oa[nxt][0] = an[0]; ob[nxt][0] = bn[0]; oa[nxt][1] = an[128]; ob[nxt][1] = bn[128];
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -576,7 +562,7 @@ winograd_conv_raw_kernel(const float* __restrict__ x, const float* __restrict__ 
             if (grp == 0) commit_slice(Un, Vn, uw, 0);
             else if (grp == 1) { commit_slice(Un, Vn, uw, 1); load_u(uw, 0); }
             else if (grp == 2) { write_raw(P ? raw1 : raw0, rq[P]); load_u(uw, 1); }
-            else { if (!(ABL & (4 | 512))) read_patch(P ? raw1 : raw0); load_raw(rq[P]); }
+            else { read_patch(P ? raw1 : raw0); load_raw(rq[P]); }
             #pragma unroll
             for (int m = 0; m < 8; ++m) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one MFMA
@@ -593,7 +579,6 @@ winograd_conv_raw_kernel(const float* __restrict__ x, const float* __restrict__ 
         }
     };
     auto first_operands = [&]() {        // of a parity-0 step, after a barrier behind the commits into buffers 0
-        if (ABL & 8) return;
         const int oidx = (ph * 8) * 128 + half * 64 + l31;
         const f32x4* a0 = smem + oidx + wm * 32;
         const f32x4* b0 = smem + 2048 + oidx + wn * 32;
@@ -612,7 +597,7 @@ winograd_conv_raw_kernel(const float* __restrict__ x, const float* __restrict__ 
     load_u(uw, 0); load_u(uw, 1);
     __syncthreads();
     first_operands();
-    if (!(ABL & 4)) read_patch(raw1);
+    read_patch(raw1);
 
     // ---- output transform y = At (m A) of a pair.  C/D layout: col = lane & 31 (tile), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) (k).
     // A wave holds rows 2 ph, 2 ph + 1 of the 4 x 4 products m and forms z = m A of both (2 values per row).  y row 0 = z0 + z1 + z2 is
@@ -649,7 +634,6 @@ winograd_conv_raw_kernel(const float* __restrict__ x, const float* __restrict__ 
         }
         const int pk = SPLIT ? pair >> cs_shift : pair;
         const int tt = pk / g.KT, kt = pk - tt * g.KT;
-        if (ABL & 32) continue;          // timing experiment: no epilogue at all (the accumulators run on)
         if (ph_u) {                      // z row 2 for the partner's y row 0
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -688,9 +672,6 @@ winograd_conv_raw_kernel(const float* __restrict__ x, const float* __restrict__ 
                     y1 = y1 > 0.f ? y1 : y1 * g.slope;
                 }
                 const unsigned vo = voff + static_cast<unsigned>(jr) * static_cast<unsigned>(HW) * 4u;
-                if (ABL & 16) {          // timing experiment: the epilogue without its global stores (one lane in a million keeps it alive)
-                    if (y0 + y1 != 12345.678f) continue;
-                }
                 if (SPLIT) {
                     // a split of the reduction: the output transform is linear, the splits' shares meet in the zero-filled output
                     // (the host only splits a call without an activation; the bias rides with split 0)
@@ -711,18 +692,10 @@ winograd_conv_raw_kernel(const float* __restrict__ x, const float* __restrict__ 
         bvec = load_bias(pair + 1);
         __syncthreads();                 // the exchange is read before the next step's commits overwrite it
     }
-    if (ABL & 32) {                      // keeps the accumulators of the epilogue-free timing variant alive
-        float t = 0.f;
-#pragma unroll
-        for (int p = 0; p < 8; ++p)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) t += acc[p][r];
-        if (t == 12345.678f) out[threadIdx.x] = t;
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------- wave-specialised variant
-// Round 5 (late).  The ablations of the kernel above (profiles/r05_winograd_pair_and_chunk_ablation.txt) say: the MFMAs with their operand
+// Round 5 (late).  Timing the kernel above with parts of its work cut out (recorded under profiles/, round 5) says: the MFMAs with their operand
 // reads and the barrier ALONE run at 98 % of the matrix pipe's bound; what costs 25-30 % is the side work -- window loads, transforms, LDS
 // commits -- sitting in the SAME in-order instruction streams: a wave that waits for an LDS read or issues stores issues no MFMAs, and
 // ~9.4 side instructions per 64-cycle MFMA slot and SIMD is the issue limit.  Here the roles are separate waves: 8 CONSUMER waves (the
@@ -732,7 +705,6 @@ winograd_conv_raw_kernel(const float* __restrict__ x, const float* __restrict__ 
 // plan (128 KiB operands + 2 x 16 KiB raw windows), same pipeline depths, one barrier per chunk, the same epilogue (the producers only
 // pass its two barriers).  Calls with a split reduction keep the kernel above.
 constexpr int kWsThreads = 768;
-template <int ABL>
 __global__ void __launch_bounds__(kWsThreads)
 winograd_conv_ws_kernel(const float* __restrict__ x, const float* __restrict__ U, const float* __restrict__ bias, float* __restrict__ out,
                         const WinoGeo g, int remap) {
@@ -763,7 +735,6 @@ winograd_conv_ws_kernel(const float* __restrict__ x, const float* __restrict__ U
             for (int r = 0; r < 16; ++r) acc[p][r] = 0.f;
         auto step = [&](auto parity) {
             constexpr int P = decltype(parity)::value;
-            if (ABL & 1) { __syncthreads(); return; }          // timing experiment: producers alone
             const f32x4* ap = smem + P * 4096 + (ph * 8) * 128 + half * 64 + wm * 32 + l31;
             const f32x4* bp = smem + P * 4096 + 2048 + (ph * 8) * 128 + half * 64 + wn * 32 + l31;
             f32x4 oa[2][2], ob[2][2];
@@ -992,12 +963,11 @@ winograd_conv_ws_kernel(const float* __restrict__ x, const float* __restrict__ U
     auto pstep = [&](auto parity) {
         constexpr int P = decltype(parity)::value, Q = 1 - P;
         f32x4* const Un = smem + Q * 4096;
-        if (ABL & 2) { __syncthreads(); return; }              // timing experiment: consumers alone
-        if (!(ABL & 4)) commit_u(Un);
-        if (!(ABL & 32)) load_u();
-        if (!(ABL & 8)) transform(Q ? raw1 : raw0, Un + 2048);
-        if (!(ABL & 16)) write_raw(P ? raw1 : raw0, rq[P]);
-        if (!(ABL & 32)) load_raw(rq[P]);
+        commit_u(Un);
+        load_u();
+        transform(Q ? raw1 : raw0, Un + 2048);
+        write_raw(P ? raw1 : raw0, rq[P]);
+        load_raw(rq[P]);
         __syncthreads();
     };
     // prologue: chunk 0 staged and transformed into buffers 0, chunk 1's window in raw[1], U(1) and the windows of chunks 2, 3 in flight
@@ -1281,39 +1251,12 @@ extern "C" int ffwm_conv3x3_winograd_forward(const void* input, const void* weig
                                 : (data_gradient ? "conv_winograd_dgrad" : "conv_winograd_fwd"), st, bytes, flops);
         if (split_n > 1 && zero_fill(output, static_cast<size_t>(B) * K * H * W * 4, st)) return FFWM_ERR_LAUNCH;
         if (rawv) {
-            auto kern = winograd_conv_raw_kernel<0>;
-            switch (options().ablate) {
-                case 1: kern = winograd_conv_raw_kernel<1>; break;
-                case 2: kern = winograd_conv_raw_kernel<2>; break;
-                case 3: kern = winograd_conv_raw_kernel<3>; break;
-                case 7: kern = winograd_conv_raw_kernel<7>; break;
-                case 16: kern = winograd_conv_raw_kernel<16>; break;
-                case 32: kern = winograd_conv_raw_kernel<32>; break;
-                case 35: kern = winograd_conv_raw_kernel<35>; break;
-                case 36: kern = winograd_conv_raw_kernel<36>; break;
-                case 39: kern = winograd_conv_raw_kernel<39>; break;
-                case 40: kern = winograd_conv_raw_kernel<40>; break;
-                case 47: kern = winograd_conv_raw_kernel<47>; break;
-                case 99: kern = winograd_conv_raw_kernel<35 + 64>; break;
-                case 163: kern = winograd_conv_raw_kernel<35 + 128>; break;
-                case 291: kern = winograd_conv_raw_kernel<35 + 256>; break;
-                case 547: kern = winograd_conv_raw_kernel<35 + 512>; break;
-                case 227: kern = winograd_conv_raw_kernel<35 + 64 + 128>; break;
-                default: break;
-            }
-            if (split_n > 1) kern = winograd_conv_raw_kernel<0, true>;
+            auto kern = split_n > 1 ? winograd_conv_raw_kernel<true> : winograd_conv_raw_kernel<false>;
             const int cus = device_cus();
             const unsigned units = nblk * static_cast<unsigned>(split_n);
             const unsigned pgrid = units < static_cast<unsigned>(cus) ? units : static_cast<unsigned>(cus);     // persistent: one workgroup per CU
             if (split_n == 1 && options().conv_wino_ws) {
-                auto wsk = winograd_conv_ws_kernel<0>;
-                if (options().ablate == 1) wsk = winograd_conv_ws_kernel<1>;
-                if (options().ablate == 2) wsk = winograd_conv_ws_kernel<2>;
-                if (options().ablate == 4) wsk = winograd_conv_ws_kernel<4>;
-                if (options().ablate == 8) wsk = winograd_conv_ws_kernel<8>;
-                if (options().ablate == 16) wsk = winograd_conv_ws_kernel<16>;
-                if (options().ablate == 32) wsk = winograd_conv_ws_kernel<32>;
-                if (options().ablate == 28) wsk = winograd_conv_ws_kernel<28>;
+                auto wsk = winograd_conv_ws_kernel;
                 allow_large_lds(reinterpret_cast<const void*>(wsk));
                 hipLaunchKernelGGL(wsk, dim3(pgrid), dim3(kWsThreads), 4 * kWinoChunk * 4 + 2 * kWinoRawFloats * 4, st,
                                    static_cast<const float*>(input), U, static_cast<const float*>(bias), static_cast<float*>(output), g, options().xcd_remap);
@@ -1327,16 +1270,7 @@ extern "C" int ffwm_conv3x3_winograd_forward(const void* input, const void* weig
             if (rc || !thin) return rc;
             }
         } else {
-        auto kern = winograd_conv_kernel<0>;
-        switch (options().ablate) {
-            case 1: kern = winograd_conv_kernel<1>; break;
-            case 2: kern = winograd_conv_kernel<2>; break;
-            case 3: kern = winograd_conv_kernel<3>; break;
-            case 4: kern = winograd_conv_kernel<4>; break;
-            case 7: kern = winograd_conv_kernel<7>; break;
-            case 15: kern = winograd_conv_kernel<15>; break;
-            default: break;
-        }
+        auto kern = winograd_conv_kernel;
         allow_large_lds(reinterpret_cast<const void*>(kern));
         hipLaunchKernelGGL(kern, dim3(nblk), dim3(kWinoThreads), 4 * kWinoChunk * 4, st, static_cast<const float*>(input), U,
                            static_cast<const float*>(bias), static_cast<float*>(output), g, options().xcd_remap);

@@ -30,7 +30,6 @@ namespace {
 
 constexpr int kGfMaxDim = 128;
 constexpr int kGfStrip = 32;          // columns per block of the column pass: a row segment is one 128-byte line
-constexpr int kGfMaxQ = 4;            // quantities per stage
 
 template <typename T>
 struct GfArgs {

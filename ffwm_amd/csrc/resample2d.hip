@@ -144,7 +144,7 @@ constexpr int kRsBoxW = 80;
 template <int HALF, int RPT, bool DB>
 __global__ void __launch_bounds__(kBlock)
 rs_fwd_lds_kernel(const float* __restrict__ in1, const float* __restrict__ in2, float* __restrict__ out, int C,
-                  int Hi, int Wi, int H, int W, int tiles_x, int tiles_y, int cslabs, int cs, int remap, int ablate) {
+                  int Hi, int Wi, int H, int W, int tiles_x, int tiles_y, int cslabs, int cs, int remap) {
     constexpr int NW = kBlock / kWave;
     constexpr int NT = 2 * HALF;                 // taps per axis
     constexpr int TH = NW * RPT;                 // tile rows
@@ -236,7 +236,7 @@ rs_fwd_lds_kernel(const float* __restrict__ in1, const float* __restrict__ in2, 
     unsigned obase[RPT];
 #pragma unroll
     for (int r = 0; r < RPT; ++r)
-        obase[r] = (inx && iny[r] && !(ablate & 2)) ? (static_cast<unsigned>(ys[r]) * W + static_cast<unsigned>(x)) * 4u : 0xFFFFFFF0u;  // OOB store is dropped
+        obase[r] = (inx && iny[r]) ? (static_cast<unsigned>(ys[r]) * W + static_cast<unsigned>(x)) * 4u : 0xFFFFFFF0u;  // OOB store is dropped
 
     // the reference's tap order: for fy, fx: TL, TR, BL, BR
     auto for_each_tap = [&](auto&& body) {
@@ -260,7 +260,7 @@ rs_fwd_lds_kernel(const float* __restrict__ in1, const float* __restrict__ in2, 
             const int i = threadIdx.x + k * kBlock;
             const int r = i / kRsBoxW, cc = i - r * kRsBoxW;
             const int gy = min(max(vmin + r, 0), Hi - 1), gx = min(max(umin + cc, 0), Wi - 1);
-            goff[k] = (r < bh && cc < bw && !(ablate & 1)) ? (static_cast<unsigned>(gy) * Wi + gx) * 4u : 0xFFFFFFF0u;   // OOB reads 0
+            goff[k] = (r < bh && cc < bw) ? (static_cast<unsigned>(gy) * Wi + gx) * 4u : 0xFFFFFFF0u;   // OOB reads 0
         }
         f32x4 stage[NI];
         auto fetch = [&](int c) {                   // channels c .. c+3 (missing ones read 0)
@@ -889,7 +889,7 @@ rs_flow_irregular_kernel(const float* __restrict__ in2, int* __restrict__ count,
 template <int HALF, int RPT, bool FIXED = false>
 __global__ void __launch_bounds__(kBlock)
 rs_bwd1_tile_kernel(const float* __restrict__ in2, const float* __restrict__ gout, float* __restrict__ gin1, int C, int Hi,
-                    int Wi, int H, int W, int quirk, int tiles_x, int tiles_y, int cslabs, int cs, int remap, int ablate,
+                    int Wi, int H, int W, int quirk, int tiles_x, int tiles_y, int cslabs, int cs, int remap,
                     const int* __restrict__ sel = nullptr, int sel_limit = 0, int sel_want = 0) {
     if (sel && ((sel[0] < sel_limit) ? 1 : 0) != sel_want) return;      // the other kernel of the pair serves this call (rs_flow_irregular_kernel)
     constexpr int NW = kBlock / kWave;
@@ -936,13 +936,7 @@ rs_bwd1_tile_kernel(const float* __restrict__ in2, const float* __restrict__ gou
         const size_t poff = static_cast<size_t>(y) * W + x;
         const float dx = fb[poff], dy = fb[plane + poff], sgm = fb[2 * plane + poff];
         RsTaps<float, HALF> t;
-        if (ablate & 8) {                  // bench-only: no Gaussian weights
-#pragma unroll
-            for (int f = 0; f < 2 * HALF; ++f) { t.wx[f] = dx; t.wy[f] = dy; }
-            t.sum = sgm;
-        } else {
-            make_rs_taps<float, HALF>(t, dx, dy, sgm, x, y, Hi, Wi, 1, quirk != 0);
-        }
+        make_rs_taps<float, HALF>(t, dx, dy, sgm, x, y, Hi, Wi, 1, quirk != 0);
         const float flx = floor_t(static_cast<float>(x) + dx), fly = floor_t(static_cast<float>(y) + dy);
         const float lim = static_cast<float>(1 << 20);
         const bool ok = (flx > -lim) && (flx < lim) && (fly > -lim) && (fly < lim);
@@ -1029,12 +1023,10 @@ rs_bwd1_tile_kernel(const float* __restrict__ in2, const float* __restrict__ gou
         unsigned long long exact = use_lds ? 0ull : ~0ull;
         if (use_lds)
         for (int c = cbase; c < cend; c += 4) {
-            if (!(ablate & 4)) {
-                if constexpr (FIXED) {
-                    for (int i = threadIdx.x; i < NCELL; i += kBlock) reinterpret_cast<int4*>(box)[i] = int4{0, 0, 0, 0};
-                } else {
-                    for (int i = threadIdx.x; i < NCELL * 2; i += kBlock) reinterpret_cast<double2*>(box)[i] = double2{0.0, 0.0};
-                }
+            if constexpr (FIXED) {
+                for (int i = threadIdx.x; i < NCELL; i += kBlock) reinterpret_cast<int4*>(box)[i] = int4{0, 0, 0, 0};
+            } else {
+                for (int i = threadIdx.x; i < NCELL * 2; i += kBlock) reinterpret_cast<double2*>(box)[i] = double2{0.0, 0.0};
             }
             const float* g0 = gp + static_cast<size_t>(c - c0) * plane;
             const rsrc_t rg0 = make_rsrc(g0, obytes);
@@ -1087,7 +1079,6 @@ rs_bwd1_tile_kernel(const float* __restrict__ in2, const float* __restrict__ gou
             for (int r = 0; r < RPT; ++r) {
                 const float gx = g[r][0], gy = g[r][1], gz = g[r][2], gw = g[r][3];
                 if (!live[r]) continue;
-                if (ablate & 1) { if (gx + gy + gz + gw == 12345.f) box[0] = 1; continue; }
                 AccT* nb = box + lbase[r];
 #pragma unroll
                 for (int pr = 0; pr < NT; ++pr)
@@ -1119,7 +1110,7 @@ rs_bwd1_tile_kernel(const float* __restrict__ in2, const float* __restrict__ gou
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const float v = FIXED ? static_cast<float>(box[q * NCELL + i]) * fx_inv[q] : static_cast<float>(box[q * NCELL + i]);
-                    if (q < nch && v != 0.f && !(ablate & 2)) atomic_add(dst + static_cast<size_t>(q) * iplane, v);
+                    if (q < nch && v != 0.f) atomic_add(dst + static_cast<size_t>(q) * iplane, v);
                 }
             }
             __syncthreads();
@@ -1135,7 +1126,7 @@ rs_bwd1_tile_kernel(const float* __restrict__ in2, const float* __restrict__ gou
 //
 // The tile kernel above lets the boxes of neighbouring blocks overlap and folds every non-zero box cell into grad_input1 with a
 // global atomic: ~1.8 per pixel and channel, which issue at about one lane per clock and CU -- 445 us of the 1.23 ms at
-// [8, 64, 512, 512] (profiles/r05_rs_bwd1_ablation.txt), an order of magnitude more per lane than an LDS atomic (4.3 clk per wave).
+// [8, 64, 512, 512] (round 5's timing breakdown under profiles/), an order of magnitude more per lane than an LDS atomic (4.3 clk per wave).
 // Here every cell of grad_input1 has exactly ONE owner: a block of 8 waves owns an OW x OH tile of the input plane (54 x 38 at ks 4)
 // and visits the 64 x 48 PIXELS of the tile grown by M = 3 + ks/2 -- every pixel whose floor offset is within +-3 of its own position
 // and can therefore reach the tile.  A pixel near a tile edge is visited by up to four blocks (x 1.5 pixel visits, x 1.5 LDS
@@ -1199,16 +1190,11 @@ struct RsFactors {
     int degenerate;
 };
 template <int HALF>
-__device__ __attribute__((noinline)) RsFactors<HALF> rs_pixel_factors(float dx, float dy, float sgm, int x, int y, int Hi, int Wi, int quirk, int ablate) {
+__device__ __attribute__((noinline)) RsFactors<HALF> rs_pixel_factors(float dx, float dy, float sgm, int x, int y, int Hi, int Wi, int quirk) {
     constexpr int NT = 2 * HALF;
     RsFactors<HALF> o;
     RsTaps<float, HALF> t;
-    if (ablate & 8) {                      // bench-only: no Gaussian weights
-#pragma unroll
-        for (int f = 0; f < NT; ++f) { t.wx[f] = dx; t.wy[f] = dy; }
-    } else {
-        make_rs_taps<float, HALF>(t, dx, dy, sgm, x, y, Hi, Wi, 1, quirk != 0);
-    }
+    make_rs_taps<float, HALF>(t, dx, dy, sgm, x, y, Hi, Wi, 1, quirk != 0);
     float wxp[NT], wyp[NT];
     float sx = 0.f, sy = 0.f;
 #pragma unroll
@@ -1226,7 +1212,7 @@ __device__ __attribute__((noinline)) RsFactors<HALF> rs_pixel_factors(float dx, 
     // every one of the NT x NT weight PRODUCTS underflowed (sigma -> 0 away from the taps; the axis sums may still be positive): the
     // reference's SAFE_DIV(wy wx, sum) is 0 for every tap -- the pixel adds nothing, as in rs_bwd1_far_kernel, and the "last = 1 -
     // others" form must not invent a weight for it
-    o.degenerate = ((ablate & 8) ? (sx == 0.f || sy == 0.f) : (t.sum == 0.f)) ? 1 : 0;
+    o.degenerate = t.sum == 0.f ? 1 : 0;
     return o;
 }
 
@@ -1246,7 +1232,7 @@ __device__ __forceinline__ unsigned rs_expo(unsigned a) {
 template <int HALF>
 __global__ void __launch_bounds__(RsOwn<HALF>::THREADS, 4)          // 16 waves per CU: 128 registers
 rs_bwd1_owned_kernel(const float* __restrict__ in2, const float* __restrict__ gout, float* __restrict__ gin1, int C, int Hi, int Wi,
-                     int H, int W, int quirk, int overwrite, int tiles_x, int tiles_y, int cslabs, int cs, int remap, int ablate) {
+                     int H, int W, int quirk, int overwrite, int tiles_x, int tiles_y, int cslabs, int cs, int remap) {
     using G = RsOwn<HALF>;
     constexpr int NT = G::NT, M = G::M, OW = G::OW, OH = G::OH, BP = G::BP, NCELL = G::NCELL, NW = G::NW, PPT = G::PPT;
     constexpr unsigned kMagicBits = 0x4B400000u;   // 1.5 * 2^23
@@ -1305,7 +1291,7 @@ rs_bwd1_owned_kernel(const float* __restrict__ in2, const float* __restrict__ go
             const float dx = fb[poff], dy = fb[plane + poff], sgm = fb[2 * plane + poff];
             ok = rs_origin<HALF>(dx, dy, x, y, u0, v0);
             if (ok) {
-                const RsFactors<HALF> fc = rs_pixel_factors<HALF>(dx, dy, sgm, x, y, Hi, Wi, quirk, ablate);
+                const RsFactors<HALF> fc = rs_pixel_factors<HALF>(dx, dy, sgm, x, y, Hi, Wi, quirk);
 #pragma unroll
                 for (int f = 0; f < NT - 1; ++f) { RS_WX(r, f) = fc.wx[f]; RS_WY(r, f) = fc.wy[f]; }
                 degenerate = fc.degenerate != 0;
@@ -1394,7 +1380,7 @@ rs_bwd1_owned_kernel(const float* __restrict__ in2, const float* __restrict__ go
     // (precision) clears the box and repeats the group with the exact exponent.  Neighbouring channels of a gradient rarely differ by
     // 8 x; when they do the group costs twice, never correctness.  The maxima are kept PER CHANNEL (exponent fields): a group whose channels
     // lie more than 2^3 apart has no exponent that resolves each of them to 2^(4 - bits) of its own maximum, and takes the exact path.
-    unsigned mb = wave_max((ablate & 4) ? 0x3F800000u : lane_max(c0));
+    unsigned mb = wave_max(lane_max(c0));
     if (lane == 0) redm[wave] = mb;
     __syncthreads();
 #pragma unroll
@@ -1467,7 +1453,6 @@ rs_bwd1_owned_kernel(const float* __restrict__ in2, const float* __restrict__ go
                         const rs_f2 wq2 = {wq, wq};
                         const rs_f2 ka = __builtin_elementwise_fma(wq2, ga, magic), kb = __builtin_elementwise_fma(wq2, gb, magic);
                         unsigned* cell = rowp + cx[pc];
-                        if (ablate & 1) { if (ka.x + ka.y + kb.x + kb.y == 12345.f) box[0] = 1; continue; }      // bench-only: no LDS atomics
                         __hip_atomic_fetch_add(cell, __float_as_uint(ka.x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                         __hip_atomic_fetch_add(cell + NCELL, __float_as_uint(ka.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                         __hip_atomic_fetch_add(cell + 2 * NCELL, __float_as_uint(kb.x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1501,7 +1486,7 @@ rs_bwd1_owned_kernel(const float* __restrict__ in2, const float* __restrict__ go
             const bool fits = ex_true <= ex && ex_min >= ex - 3 && ex_true > -80 && ex_true < 120;
             usable = !exact_path && (emax == 0u || fits);
             ex_assumed = emax != 0u && !exact_path ? ex_true + 1 : ex;       // the next group's assumption
-            if (!usable && !exact_path && !(ablate & 4)) {
+            if (!usable && !exact_path) {
                 // no single exponent serves the group: channels more than 2^3 apart, or magnitudes outside the clamp of the scale
                 const bool hopeless = ex_min < ex_true - 3 || ex_true <= -80 || ex_true >= 120;
                 if (repeated || hopeless) {
@@ -1517,7 +1502,6 @@ rs_bwd1_owned_kernel(const float* __restrict__ in2, const float* __restrict__ go
             }
         }
         repeated = false;
-        if (!usable && !exact_path) usable = true;      // (ablate & 4 only)
         // flush the owned cells: plain coalesced stores, no other block touches them
         for (int i = threadIdx.x; i < OW * OH; i += G::THREADS) {
             const int rr = i / OW, cc = i - rr * OW;
@@ -1530,7 +1514,7 @@ rs_bwd1_owned_kernel(const float* __restrict__ in2, const float* __restrict__ go
             for (int q = 0; q < 4; ++q) {
                 const float v = usable ? static_cast<float>(static_cast<int>(box[q * NCELL + bi] - nb)) * fx_inv : 0.f;
                 box[q * NCELL + bi] = 0;
-                if (q < nch && in_img && !(ablate & 2)) {
+                if (q < nch && in_img) {
                     float* d = dst + static_cast<size_t>(q) * iplane;
                     if (overwrite) *d = v;
                     else if (v != 0.f) atomic_add(d, v);        // `+=` mode: a return-less atomic (one transaction), not a read-modify-write round trip (measured: +260 us)
@@ -1667,7 +1651,7 @@ rs_bwd1_far_kernel(const float* __restrict__ in2, const float* __restrict__ gout
 template <int RPT, int NW>
 __global__ void __launch_bounds__(NW * kWave)
 rs_bwd1_taplane_kernel(const float* __restrict__ in2, const float* __restrict__ gout, float* __restrict__ gin1, int C, int Hi,
-                       int Wi, int H, int W, int quirk, int tiles_x, int tiles_y, int cslabs, int cs, int remap, int ablate,
+                       int Wi, int H, int W, int quirk, int tiles_x, int tiles_y, int cslabs, int cs, int remap,
                        const int* __restrict__ sel = nullptr, int sel_limit = 0, int sel_want = 0) {
     if (sel && ((sel[0] < sel_limit) ? 1 : 0) != sel_want) return;      // the other kernel of the pair serves this call
     constexpr int HALF = 2;
@@ -1792,7 +1776,7 @@ rs_bwd1_taplane_kernel(const float* __restrict__ in2, const float* __restrict__ 
 #pragma unroll
                 for (int k = 0; k < NTAP; ++k) wS[k * SP + lane] = wn[r][k];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) gS[q * SP + lane] = (ablate & 16) ? 1.f : gv[r][q];
+                for (int q = 0; q < 4; ++q) gS[q * SP + lane] = gv[r][q];
                 __builtin_amdgcn_wave_barrier();
                 const int lb = lbase[r];
                 // batches of 8 pixels, the next batch's weights and gradients read before this batch's atomics are issued (the
@@ -1807,7 +1791,6 @@ rs_bwd1_taplane_kernel(const float* __restrict__ in2, const float* __restrict__ 
                 auto emit = [&](int px0, const float (&wv)[NB], const float (&gq)[NB]) {
 #pragma unroll
                     for (int k = 0; k < NB; ++k) {
-                        if (ablate & 1) { if (wv[k] * gq[k] == 12345.f) box[0] = 1; continue; }     // bench-only: no LDS atomics
                         lds_add(mycell + __builtin_amdgcn_readlane(lb, px0 + k), wv[k] * gq[k]);
                     }
                 };
@@ -1832,7 +1815,7 @@ rs_bwd1_taplane_kernel(const float* __restrict__ in2, const float* __restrict__ 
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const float v = static_cast<float>(box[q * PS + i]);
-                    if (q < nch && v != 0.f && !(ablate & 2)) atomic_add(dst + static_cast<size_t>(q) * iplane, v);
+                    if (q < nch && v != 0.f) atomic_add(dst + static_cast<size_t>(q) * iplane, v);
                 }
             }
             __syncthreads();
@@ -2077,7 +2060,7 @@ int launch_fwd(const T* in1, const T* in2, T* out, int64_t B, int64_t C, int64_t
     do {                                                                                                   \
         allow_large_lds(reinterpret_cast<const void*>(rs_fwd_lds_kernel<HH, RR, DD>));                     \
         hipLaunchKernelGGL((rs_fwd_lds_kernel<HH, RR, DD>), dim3(grid), dim3(kBlock), lds, st, in1, in2, out, \
-                           (int)C, (int)Hi, (int)Wi, (int)H, (int)W, tiles_x, tiles_y, cslabs, cs, remap, options().ablate); \
+                           (int)C, (int)Hi, (int)Wi, (int)H, (int)W, tiles_x, tiles_y, cslabs, cs, remap); \
     } while (0)
 #define FFWM_RS_FWD_LDS_H(RR, DD)                                                                          \
     do {                                                                                                   \
@@ -2149,10 +2132,10 @@ int launch_bwd(const T* in1, const T* in2, const T* gout, T* gin1, T* gin2, int6
 #endif
                 if (half == 1)
                     hipLaunchKernelGGL((rs_bwd1_owned_kernel<1>), dim3(grid), dim3(RsOwn<1>::THREADS), lds1, st, (const float*)in2, (const float*)gout,
-                                       (float*)gin1, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, quirk, overwrite ? 1 : 0, tiles_x, tiles_y, cslabs, cs, remap, options().ablate);
+                                       (float*)gin1, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, quirk, overwrite ? 1 : 0, tiles_x, tiles_y, cslabs, cs, remap);
                 else
                     hipLaunchKernelGGL((rs_bwd1_owned_kernel<2>), dim3(grid), dim3(RsOwn<2>::THREADS), lds2, st, (const float*)in2, (const float*)gout,
-                                       (float*)gin1, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, quirk, overwrite ? 1 : 0, tiles_x, tiles_y, cslabs, cs, remap, options().ablate);
+                                       (float*)gin1, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, quirk, overwrite ? 1 : 0, tiles_x, tiles_y, cslabs, cs, remap);
             }
             if (int rc = check_launch("ffwm_resample2d_backward(input1, owned tiles)")) return rc;
             {
@@ -2234,11 +2217,11 @@ int launch_bwd(const T* in1, const T* in2, const T* gout, T* gin1, T* gin2, int6
                 if (nw == 8) {
                     allow_large_lds(reinterpret_cast<const void*>(rs_bwd1_taplane_kernel<2, 8>));
                     hipLaunchKernelGGL((rs_bwd1_taplane_kernel<2, 8>), dim3(grid), dim3(8 * kWave), lds, st, in2, gout, gin1, (int)C, (int)Hi,
-                                       (int)Wi, (int)H, (int)W, quirk, tiles_x, tiles_y, cslabs, cs, remap, options().ablate, sel, sel_limit, 0);
+                                       (int)Wi, (int)H, (int)W, quirk, tiles_x, tiles_y, cslabs, cs, remap, sel, sel_limit, 0);
                 } else {
                     allow_large_lds(reinterpret_cast<const void*>(rs_bwd1_taplane_kernel<2, 4>));
                     hipLaunchKernelGGL((rs_bwd1_taplane_kernel<2, 4>), dim3(grid), dim3(4 * kWave), lds, st, in2, gout, gin1, (int)C, (int)Hi,
-                                       (int)Wi, (int)H, (int)W, quirk, tiles_x, tiles_y, cslabs, cs, remap, options().ablate, sel, sel_limit, 0);
+                                       (int)Wi, (int)H, (int)W, quirk, tiles_x, tiles_y, cslabs, cs, remap, sel, sel_limit, 0);
                 }
                 if (int rc = check_launch("ffwm_resample2d_backward(input1, tap-lane)")) return rc;
             }
@@ -2256,7 +2239,7 @@ int launch_bwd(const T* in1, const T* in2, const T* gout, T* gin1, T* gin2, int6
     do {                                                                                                      \
         allow_large_lds(reinterpret_cast<const void*>(rs_bwd1_tile_kernel<HH, RR, FX>));                      \
         hipLaunchKernelGGL((rs_bwd1_tile_kernel<HH, RR, FX>), dim3(grid), dim3(kBlock), lds, st, in2, gout, gin1, (int)C, \
-                           (int)Hi, (int)Wi, (int)H, (int)W, quirk, tiles_x, tiles_y, cslabs, cs, remap, options().ablate, \
+                           (int)Hi, (int)Wi, (int)H, (int)W, quirk, tiles_x, tiles_y, cslabs, cs, remap, \
                            adaptive ? sel : nullptr, sel_limit, 1); \
     } while (0)
 #define FFWM_RS_B1T(HH, RR) do { if (fixed_cells) FFWM_RS_B1T_(HH, RR, true); else FFWM_RS_B1T_(HH, RR, false); } while (0)

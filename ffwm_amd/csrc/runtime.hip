@@ -289,7 +289,6 @@ int ffwm_set_option(const char* key, int value) {
     else if (!strcmp(key, "be_bwd_variant")) slot = &o.be_bwd_variant;
     else if (!strcmp(key, "channel_slab")) slot = &o.channel_slab;
     else if (!strcmp(key, "xcd_remap")) slot = &o.xcd_remap;
-    else if (!strcmp(key, "ablate")) slot = &o.ablate;
     else if (!strcmp(key, "warp_multi_order")) slot = &o.warp_multi_order;
     else if (!strcmp(key, "rows_per_thread")) slot = &o.rows_per_thread;
     else if (!strcmp(key, "scatter_variant")) slot = &o.scatter_variant;
@@ -311,7 +310,6 @@ int ffwm_set_option(const char* key, int value) {
     else if (!strcmp(key, "conv_fwd_split_target")) slot = &o.conv_fwd_split_target;
     else if (!strcmp(key, "conv_wino_split")) slot = &o.conv_wino_split;
     else if (!strcmp(key, "conv_wgrad_unsliced")) slot = &o.conv_wgrad_unsliced;
-    else if (!strcmp(key, "conv_wgrad_prezeroed")) slot = &o.conv_wgrad_prezeroed;
     else if (!strcmp(key, "zero_fill_memset")) slot = &o.zero_fill_memset;
     else if (!strcmp(key, "be_bwd_fixed")) slot = &o.be_bwd_fixed;
     else if (!strcmp(key, "be_bwd_flush")) slot = &o.be_bwd_flush;
@@ -329,6 +327,10 @@ int ffwm_set_option(const char* key, int value) {
     else if (!strcmp(key, "conv_fwd_kfast")) slot = &o.conv_fwd_kfast;
     if (!slot) {
         set_error("ffwm_set_option: unknown key '%s'", key);
+        return FFWM_ERR_ARG;
+    }
+    if (value < 0) {
+        set_error("ffwm_set_option: negative value %d for '%s'", value, key);
         return FFWM_ERR_ARG;
     }
     int prev = *slot;

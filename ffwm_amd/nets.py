@@ -9,10 +9,7 @@ flow-guided warp inside netG's warp-attention module goes through the hand-writt
 (``WarpFlipCat``: grid_sample + flip + concat in one pass).
 """
 import math
-
 import os
-
-import os as _os
 
 import torch
 import torch.nn as nn
@@ -221,7 +218,7 @@ class FFWM(nn.Module):
         self._fused = warp_flipcat if warp_flipcat is not None else WarpFlipCat()
         # the HIP path: all levels' warps in one multi-problem launch (FFWM_WARP_MULTI=0: a launch per level, issued where the decoder needs
         # it -- its backward then runs right behind the attention convs' that produced its grad_output, on warm caches)
-        self._multi = warp_flipcat is None and _os.environ.get("FFWM_WARP_MULTI", "1") != "0"
+        self._multi = warp_flipcat is None and os.environ.get("FFWM_WARP_MULTI", "1") != "0"
         self.fuse_gate = False                       # residual.fuse_residual: `skip * att_i(skip)` with its sigmoid tail as one kernel
 
     def _skip(self, feat, flow):

@@ -519,10 +519,9 @@ int ffwm_prof_get_flops(int row, double* algorithmic_flops);
 int ffwm_prof_get_bound(int row, double* roofline_ms);
 int ffwm_prof_reset(void);
 
-/* Tuning/ablation switches (bench and tests only): returns the previous value, or
- * FFWM_ERR_ARG for an unknown key.  Keys: "be_fwd_variant", "be_bwd_variant",
- * "channel_slab", "xcd_remap", "ablate", "rows_per_thread",
- * "scatter_variant". */
+/* Tuning switches (bench and tests only; the keys are the members of struct Options in ffwm_amd/csrc/common.hpp).  Returns the
+ * previous value of the option.  No option gives a negative value a meaning: an unknown key or value < 0 changes nothing and
+ * returns FFWM_ERR_ARG, so a negative return is always an error. */
 int ffwm_set_option(const char* key, int value);
 
 /* Zero-fill `bytes` bytes (a multiple of 4) at the 4-byte aligned device address `p` with a KERNEL on `stream` -- what the

@@ -56,6 +56,18 @@ def test_argument_errors_are_reported_before_launch(hiplib):
     rc = hiplib.ffwm_warp_forward(p, p, p, 1, 1, 1 << 15, 1 << 15, 4, 4, 0, 0, None)
     assert rc == -3
     assert hiplib.ffwm_set_option(b"no_such_key", 1) == -1
+    # options that no longer exist are unknown keys like any other
+    assert hiplib.ffwm_set_option(b"ablate", 1) == -1 and b"unknown key" in hiplib.ffwm_last_error()
+    assert hiplib.ffwm_set_option(b"conv_wgrad_prezeroed", 1) == -1
+    # no option gives a negative value a meaning: refused, the option keeps its value (a negative return is always an error)
+    assert hiplib.ffwm_set_option(b"xcd_remap", -1) == -1 and b"negative" in hiplib.ffwm_last_error()
+    assert hiplib.ffwm_set_option(b"xcd_remap", 1) == 1
+    from ffwm_amd import _lib
+    with pytest.raises(_lib.FFWMError):
+        _lib.set_option("ablate", 1)
+    with pytest.raises(_lib.FFWMError):
+        _lib.set_option("xcd_remap", -1)
+    assert _lib.set_option("xcd_remap", 1) == 1
     # the convolution entry points: argument checks come before any launch
     rc = hiplib.ffwm_conv3x3_winograd_forward(None, None, None, None, None, 1, 8, 4, 4, 8, 0, 0, 0.0, 0, None)
     assert rc == -1 and b"NULL" in hiplib.ffwm_last_error()
