@@ -1810,6 +1810,9 @@ be_bwd_generic(const T* __restrict__ src, const T* __restrict__ flow, const T* _
 }
 
 // ------------------------------------------------------------------------------ host
+// Grid of the per-element (grid-stride) kernels over n elements, at most `cap` blocks.
+inline unsigned element_grid(int64_t n, int cap) { return capped_grid(n / kBlock + 1, cap); }
+
 template <typename T>
 int launch_fwd(const T* src, const T* flow, T* out, int64_t B, int64_t C, int64_t Hs, int64_t Ws,
                int64_t Hf, int64_t Wf, int k, hipStream_t st) {
@@ -1818,50 +1821,69 @@ int launch_fwd(const T* src, const T* flow, T* out, int64_t B, int64_t C, int64_
     const int remap = options().xcd_remap;
     // an output that cannot stay in L2 / MALL anyway is written with streaming (nt) stores: 4.9 -> 5.7 TB/s on cfg-5
     const int nt = static_cast<double>(sizeof(T)) * B * C * k * k * Hf * Wf >= 64.0 * 1024 * 1024 ? 1 : 0;
-    // variant: 0 = auto (LDS-staged for k <= 4, direct gather above), 1 = direct gather, 2 = LDS-staged
+    // be_fwd_variant: 0 = auto (LDS-staged for k <= 4, direct gather above), 1 = direct gather, 2 = LDS-staged, 9 = per-element kernel
     const int variant = options().be_fwd_variant;
-#define FFWM_BE_FWD(KK)                                                                            \
-    case KK: {                                                                                     \
-        const bool lds = KK <= 4 && (variant == 2 || variant == 0);                              \
-        LaunchScope ls(lds ? "block_extractor_fwd_lds" : "block_extractor_fwd", st, bytes);        \
-        if (lds) {                                                                                 \
-            const int rpt = sizeof(T) == 8 ? 1 : (options().rows_per_thread > 0 ? options().rows_per_thread : (Hf >= 64 ? 4 : 1)); \
-            const int th = (kBlock / kWave) * (rpt >= 4 ? 4 : (rpt >= 2 ? 2 : 1));                  \
-            const int tyl = static_cast<int>((Hf + th - 1) / th);                                  \
-            const unsigned gridl = static_cast<unsigned>(B * g.tiles_x * tyl * g.cslabs);           \
-            if (rpt >= 4)                                                                          \
-                hipLaunchKernelGGL((be_fwd_lds_kernel<float, (KK <= 4 ? KK : 1), 4>), dim3(gridl),  \
-                                   dim3(kBlock), 0, st, (const float*)src, (const float*)flow,     \
-                                   (float*)out, (int)C, (int)Hs, (int)Ws,                          \
-                                   (int)Hf, (int)Wf, g.tiles_x, tyl, g.cslabs, g.cs, remap, nt);   \
-            else if (rpt >= 2)                                                                     \
-                hipLaunchKernelGGL((be_fwd_lds_kernel<float, (KK <= 4 ? KK : 1), 2>), dim3(gridl),  \
-                                   dim3(kBlock), 0, st, (const float*)src, (const float*)flow,     \
-                                   (float*)out, (int)C, (int)Hs, (int)Ws,                          \
-                                   (int)Hf, (int)Wf, g.tiles_x, tyl, g.cslabs, g.cs, remap, nt);   \
-            else                                                                                   \
-                hipLaunchKernelGGL((be_fwd_lds_kernel<T, (KK <= 4 ? KK : 1), 1>), dim3(gridl),      \
-                                   dim3(kBlock), 0, st, src, flow, out, (int)C, (int)Hs, (int)Ws,  \
-                                   (int)Hf, (int)Wf, g.tiles_x, tyl, g.cslabs, g.cs, remap, nt);   \
-        } else                                                                                       \
-            hipLaunchKernelGGL((be_fwd_kernel<T, KK>), dim3(g.grid), dim3(kBlock), 0, st, src,     \
-                               flow, out, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, g.tiles_x,   \
-                               g.tiles_y, g.cslabs, g.cs, remap);                                  \
-    } break;
-    const bool generic = options().be_fwd_variant == 9;
-    switch (generic ? 0 : k) {
-        FFWM_BE_FWD(1) FFWM_BE_FWD(2) FFWM_BE_FWD(3) FFWM_BE_FWD(4) FFWM_BE_FWD(5) FFWM_BE_FWD(6)
-        FFWM_BE_FWD(7)
-        default: {
-            const int64_t n = B * C * k * Hf * k * Wf;
-            const unsigned grid = static_cast<unsigned>(n / kBlock + 1 < 16384 ? n / kBlock + 1 : 16384);
-            LaunchScope ls("block_extractor_fwd_generic", st, bytes);
-            hipLaunchKernelGGL((be_fwd_generic<T>), dim3(grid), dim3(kBlock), 0, st, src, flow, out,
-                               n, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, k);
-        }
+    const bool generic = variant == 9 || k > 7;
+    const bool lds = !generic && k <= 4 && (variant == 2 || variant == 0);
+    bool ok = true;          // false: a dispatch below found no kernel for its value
+    if (lds) {
+        // pixel rows per thread: 4 / 2 / 1 (float64: always 1)
+        const int want = sizeof(T) == 8 ? 1 : (options().rows_per_thread > 0 ? options().rows_per_thread : (Hf >= 64 ? 4 : 1));
+        LaunchScope ls("block_extractor_fwd_lds", st, bytes);
+        ok &= dispatch<1, 2, 3, 4>(k, [&](auto K) {
+            return dispatch<4, 2, 1>(want >= 4 ? 4 : (want >= 2 ? 2 : 1), [&](auto RPT) {
+                constexpr int TH = (kBlock / kWave) * RPT.value;
+                const int tyl = static_cast<int>((Hf + TH - 1) / TH);
+                const unsigned gridl = static_cast<unsigned>(B * g.tiles_x * tyl * g.cslabs);
+                if constexpr (RPT.value == 1)
+                    hipLaunchKernelGGL((be_fwd_lds_kernel<T, K.value, 1>), dim3(gridl), dim3(kBlock), 0, st, src, flow, out, (int)C, (int)Hs, (int)Ws,
+                                       (int)Hf, (int)Wf, g.tiles_x, tyl, g.cslabs, g.cs, remap, nt);
+                else          // (more than one row per thread: float only)
+                    hipLaunchKernelGGL((be_fwd_lds_kernel<float, K.value, RPT.value>), dim3(gridl), dim3(kBlock), 0, st, (const float*)src,
+                                       (const float*)flow, (float*)out, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, g.tiles_x, tyl, g.cslabs, g.cs,
+                                       remap, nt);
+            });
+        });
+    } else if (!generic) {
+        LaunchScope ls("block_extractor_fwd", st, bytes);
+        ok &= dispatch<1, 2, 3, 4, 5, 6, 7>(k, [&](auto K) {
+            hipLaunchKernelGGL((be_fwd_kernel<T, K.value>), dim3(g.grid), dim3(kBlock), 0, st, src, flow, out, (int)C, (int)Hs, (int)Ws, (int)Hf,
+                               (int)Wf, g.tiles_x, g.tiles_y, g.cslabs, g.cs, remap);
+        });
+    } else {
+        const int64_t n = B * C * k * Hf * k * Wf;
+        LaunchScope ls("block_extractor_fwd_generic", st, bytes);
+        hipLaunchKernelGGL((be_fwd_generic<T>), dim3(element_grid(n, 16384)), dim3(kBlock), 0, st, src, flow, out,
+                           n, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, k);
     }
-#undef FFWM_BE_FWD
-    return check_launch("ffwm_block_extractor_forward");
+    return ok ? check_launch("ffwm_block_extractor_forward") : no_kernel("ffwm_block_extractor_forward");
+}
+
+// The tile kernels of the backward (fp32, k <= 4, a plane too large for the LDS-plane kernel), one type per configuration:
+//   SHARED  be_bwd_tile2_kernel<K, RH, HALO, FIXED>: tiles of 64 x RH cells without halo revisits, atomic flush (+ be_bwd_far2_kernel)
+//   else    be_bwd_tile_kernel<K, RH, HALO>: owned tiles (halo revisits, plain stores) (+ be_bwd_far_kernel)
+// HALO 4 (|tap offset| <= 4 stays on the fast path) or 8; region height RH 32 or 64 rows; FIXED = 32-bit fixed-point accumulator
+// cells (round 5) instead of the double cells of rounds 2-4.  The kernel's template arguments and the TileGeo both kernels of a call
+// agree on come from the same members.
+template <bool SHARED_, int RH_, int HALO_, bool FIXED_ = false>
+struct BeTile {
+    static constexpr bool SHARED = SHARED_, FIXED = FIXED_;
+    static constexpr int RH = RH_, HALO = HALO_;
+    static constexpr TileGeo geo() { return SHARED ? TileGeo{kTileRW, RH, HALO, RH} : TileGeo{kTileRW - 2 * HALO, RH - 2 * HALO, HALO, RH}; }
+};
+// be_bwd_variant 0 / 3 = shared cells, 2 = owned tiles; be_bwd_halo > 4: halo 8; be_bwd_fixed 2: double cells (shared cells, halo 4);
+// be_bwd_rows 64: 64-row regions (owned tiles, halo 4, k = 3 only)
+template <class F>
+void select_be_tile(int k, F&& f) {
+    const Options& o = options();
+    const bool halo8 = o.be_bwd_halo > 4;
+    if (o.be_bwd_variant != 2) {
+        if (halo8) f(BeTile<true, 32, 8>{});
+        else if (o.be_bwd_fixed != 2) f(BeTile<true, 32, 4, true>{});
+        else f(BeTile<true, 32, 4>{});
+    } else if (!halo8 && k == 3 && o.be_bwd_rows == 64) f(BeTile<false, 64, 4>{});
+    else if (halo8) f(BeTile<false, 32, 8>{});
+    else f(BeTile<false, 32, 4>{});
 }
 
 template <typename T>
@@ -1869,10 +1891,24 @@ int launch_bwd(const T* src, const T* flow, const T* gout, T* gsrc, T* gflow, in
                int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, int k, hipStream_t st) {
     const double bytes = sizeof(T) * static_cast<double>(B) * (static_cast<double>(C) * k * k * Hf * Wf + 2.0 * C * Hs * Ws + 4.0 * Hf * Wf);
     const size_t plane_lds = static_cast<size_t>(Hs) * Ws * sizeof(double);     // the LDS accumulator is double
-    if (gsrc && plane_lds <= 131072 && options().scatter_variant != 1 && options().be_bwd_variant != 9) {
+    const int remap = options().xcd_remap;
+    // The route.  be_bwd_variant: 0 = auto (3), 1 = all-atomic pixel kernel, 2 = owned tiles (halo revisits, plain stores),
+    //             3 = shared-cell tiles (no revisits, atomic flush), 9 = generic
+    const int variant = options().be_bwd_variant;
+    // d(source) of a plane that fits LDS: the plane kernel; d(flow), when wanted too, by the pixel-major kernel
+    const bool src_plane = gsrc && plane_lds <= 131072 && options().scatter_variant != 1 && variant != 9;
+    // else float, k <= 4: the tile kernels, which produce d(flow) as well
+    const bool tiles = sizeof(T) == 4 && gsrc && !src_plane && k >= 1 && k <= 4 && (variant == 0 || variant == 2 || variant == 3);
+    // everything left: the pixel-major kernel (k <= 7) or the per-element one
+    const bool pixels = !tiles && (gflow || !src_plane);
+    T* const gsrc_px = src_plane ? nullptr : gsrc;
+    bool ok = true;          // false: a dispatch below found no kernel for its value
+    const bool generic = variant == 9 || k > 7;
+
+    if (src_plane) {
         int cg = static_cast<int>(131072 / plane_lds);
         if (cg > C) cg = static_cast<int>(C);
-        while (cg > 1 && B * ((C + cg - 1) / cg) < 512) cg = (cg + 1) / 2;
+        cg = halve_slab(cg, C, B, 512, 1);
         const int groups = static_cast<int>((C + cg - 1) / cg);
         int nsplit = 1;
         while (B * groups * nsplit < 256 && nsplit * 2 * kPlaneThreads <= Hf * Wf) nsplit *= 2;
@@ -1885,105 +1921,70 @@ int launch_bwd(const T* src, const T* flow, const T* gout, T* gsrc, T* gflow, in
                                (int)Hf, (int)Wf, k, cg, groups, nsplit);
         }
         if (int rc = check_launch("ffwm_block_extractor_backward(source, plane)")) return rc;
-        if (!gflow) return FFWM_OK;
-        gsrc = nullptr;    // the pixel-major kernel below now only produces d(flow)
     }
-    const int remap = options().xcd_remap;
-    // owned-tile path: float, k <= 4, grad_source wanted, plane too large for the LDS-plane kernel
-    // be_bwd_variant: 0 = auto (3), 1 = all-atomic pixel kernel, 2 = owned tiles (halo revisits, plain stores),
-    //                 3 = shared-cell tiles (no revisits, atomic flush), 9 = generic
     if constexpr (sizeof(T) == 4) {
-        const int variant = options().be_bwd_variant;
-        if (gsrc && k >= 1 && k <= 4 && (variant == 0 || variant == 2 || variant == 3)) {
-            // halo 4 (|tap offset| <= 4 stays on the fast path) or 8; region height 32 or 64 rows
-            const int h = options().be_bwd_halo > 4 ? 8 : 4;
-            const bool shared_cells = variant == 0 || variant == 3;      // tiles without halo revisits + atomic flush
-            const int RH = (!shared_cells && h == 4 && k == 3 && options().be_bwd_rows == 64) ? 64 : 32;
-            const TileGeo geo = shared_cells ? TileGeo{kTileRW, RH, h, RH} : TileGeo{kTileRW - 2 * h, RH - 2 * h, h, RH};
-            const int ntx = static_cast<int>(((Ws > Wf ? Ws : Wf) + geo.TW - 1) / geo.TW);
-            const int nty = static_cast<int>(((Hs > Hf ? Hs : Hf) + geo.TH - 1) / geo.TH);
-            int cs = options().channel_slab > 0 ? options().channel_slab : 4;
-            if (cs > C) cs = static_cast<int>(C);
-            while (cs > 4 && B * ntx * nty * ((C + cs - 1) / cs) < 1536) cs = (cs + 1) / 2;   // >= 6 blocks per CU
-            const int cslabs = static_cast<int>((C + cs - 1) / cs);
-            const Geometry gf = plan(B, C, Hf, Wf, 32);
-            {
-                LaunchScope ls("block_extractor_bwd_far", st, sizeof(T) * 2.0 * B * Hf * Wf);
-                switch (k) {
-#define FFWM_BE_FAR(KK)                                                                                       \
-    case KK:                                                                                                  \
-        if (shared_cells)                                                                                     \
-            hipLaunchKernelGGL((be_bwd_far2_kernel<float, KK>), dim3(gf.grid), dim3(kBlock), 0, st, (const float*)flow, \
-                               (const float*)gout, (float*)gsrc, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf,  \
-                               gf.tiles_x, gf.tiles_y, gf.cslabs, gf.cs, geo);                                \
-        else                                                                                                  \
-            hipLaunchKernelGGL((be_bwd_far_kernel<float, KK>), dim3(gf.grid), dim3(kBlock), 0, st, (const float*)flow, \
-                               (const float*)gout, (float*)gsrc, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf,  \
-                               gf.tiles_x, gf.tiles_y, gf.cslabs, gf.cs, geo);                                \
-        break;
-                    FFWM_BE_FAR(1) FFWM_BE_FAR(2) FFWM_BE_FAR(3) FFWM_BE_FAR(4)
-#undef FFWM_BE_FAR
+        if (tiles) {
+            int rc = FFWM_OK;
+            select_be_tile(k, [&](auto cfg) {
+                using Cfg = decltype(cfg);
+                constexpr TileGeo geo = Cfg::geo();
+                const int ntx = static_cast<int>(((Ws > Wf ? Ws : Wf) + geo.TW - 1) / geo.TW);
+                const int nty = static_cast<int>(((Hs > Hf ? Hs : Hf) + geo.TH - 1) / geo.TH);
+                int cs = options().channel_slab > 0 ? options().channel_slab : 4;
+                if (cs > C) cs = static_cast<int>(C);
+                cs = halve_slab(cs, C, B * ntx * nty, 1536, 4);   // >= 6 blocks per CU
+                const int cslabs = static_cast<int>((C + cs - 1) / cs);
+                const Geometry gf = plan(B, C, Hf, Wf, 32);
+                {
+                    LaunchScope ls("block_extractor_bwd_far", st, sizeof(T) * 2.0 * B * Hf * Wf);
+                    ok &= dispatch<1, 2, 3, 4>(k, [&](auto K) {
+                        if constexpr (Cfg::SHARED)
+                            hipLaunchKernelGGL((be_bwd_far2_kernel<float, K.value>), dim3(gf.grid), dim3(kBlock), 0, st, (const float*)flow,
+                                               (const float*)gout, (float*)gsrc, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, gf.tiles_x, gf.tiles_y,
+                                               gf.cslabs, gf.cs, geo);
+                        else
+                            hipLaunchKernelGGL((be_bwd_far_kernel<float, K.value>), dim3(gf.grid), dim3(kBlock), 0, st, (const float*)flow,
+                                               (const float*)gout, (float*)gsrc, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, gf.tiles_x, gf.tiles_y,
+                                               gf.cslabs, gf.cs, geo);
+                    });
                 }
-            }
-            if (int rc = check_launch("ffwm_block_extractor_backward(far)")) return rc;
-            {
-                LaunchScope ls(shared_cells ? "block_extractor_bwd_tile2" : "block_extractor_bwd_tile", st, bytes);
+                if ((rc = ok ? check_launch("ffwm_block_extractor_backward(far)") : no_kernel("ffwm_block_extractor_backward(far)"))) return;
+                LaunchScope ls(Cfg::SHARED ? "block_extractor_bwd_tile2" : "block_extractor_bwd_tile", st, bytes);
                 const unsigned grid = static_cast<unsigned>(B * ntx * nty * cslabs);
-                const bool fixed_cells = options().be_bwd_fixed != 2;        // 32-bit fixed-point accumulator cells (round 5); 2 = the double cells of rounds 2-4
-                const int flush_rmw = options().be_bwd_flush == 1 ? 1 : 0;   // 1 = interior cells by read-modify-write (round 6 experiment: SLOWER, profiles/r06_be_flush_rmw_negative.txt); 0 = every cell by a global atomic
-#define FFWM_BE_TILE(KERNEL, KK, RR, HH)                                                                      \
-    hipLaunchKernelGGL((KERNEL<KK, RR, HH>), dim3(grid), dim3(kBlock), 0, st, (const float*)src,              \
-                       (const float*)flow, (const float*)gout, (float*)gsrc, (float*)gflow, (int)C, (int)Hs,  \
-                       (int)Ws, (int)Hf, (int)Wf, ntx, nty, cslabs, cs, remap)
-#define FFWM_BE_TILE2(KK, RR, HH, FIXED)                                                                      \
-    hipLaunchKernelGGL((be_bwd_tile2_kernel<KK, RR, HH, FIXED>), dim3(grid), dim3(kBlock), 0, st, (const float*)src, \
-                       (const float*)flow, (const float*)gout, (float*)gsrc, (float*)gflow, (int)C, (int)Hs,  \
-                       (int)Ws, (int)Hf, (int)Wf, ntx, nty, cslabs, cs, remap, flush_rmw)
-#define FFWM_BE_TILE_K(KK)                                                                                    \
-    case KK:                                                                                                  \
-        if (shared_cells) {                                                                                   \
-            if (h == 8) FFWM_BE_TILE2(KK, 32, 8, false);                                                      \
-            else if (fixed_cells) FFWM_BE_TILE2(KK, 32, 4, true);                                             \
-            else FFWM_BE_TILE2(KK, 32, 4, false);                                                             \
-        } else {                                                                                              \
-            if (h == 8) FFWM_BE_TILE(be_bwd_tile_kernel, KK, 32, 8);                                          \
-            else FFWM_BE_TILE(be_bwd_tile_kernel, KK, 32, 4);                                                 \
-        }                                                                                                     \
-        break;
-                if (RH == 64) {
-                    FFWM_BE_TILE(be_bwd_tile_kernel, 3, 64, 4);
-                } else {
-                    switch (k) { FFWM_BE_TILE_K(1) FFWM_BE_TILE_K(2) FFWM_BE_TILE_K(3) FFWM_BE_TILE_K(4) }
-                }
-#undef FFWM_BE_TILE_K
-#undef FFWM_BE_TILE2
-#undef FFWM_BE_TILE
-            }
-            return check_launch("ffwm_block_extractor_backward(tile)");
+                auto launch_k = [&](auto K) {
+                    if constexpr (Cfg::SHARED) {
+                        // 1 = interior cells by read-modify-write (round 6 experiment: SLOWER, profiles/r06_be_flush_rmw_negative.txt); 0 = every cell by a global atomic
+                        const int flush_rmw = options().be_bwd_flush == 1 ? 1 : 0;
+                        hipLaunchKernelGGL((be_bwd_tile2_kernel<K.value, Cfg::RH, Cfg::HALO, Cfg::FIXED>), dim3(grid), dim3(kBlock), 0, st, (const float*)src,
+                                           (const float*)flow, (const float*)gout, (float*)gsrc, (float*)gflow, (int)C, (int)Hs, (int)Ws, (int)Hf,
+                                           (int)Wf, ntx, nty, cslabs, cs, remap, flush_rmw);
+                    } else {
+                        hipLaunchKernelGGL((be_bwd_tile_kernel<K.value, Cfg::RH, Cfg::HALO>), dim3(grid), dim3(kBlock), 0, st, (const float*)src,
+                                           (const float*)flow, (const float*)gout, (float*)gsrc, (float*)gflow, (int)C, (int)Hs, (int)Ws, (int)Hf,
+                                           (int)Wf, ntx, nty, cslabs, cs, remap);
+                    }
+                };
+                if constexpr (Cfg::RH == 64) launch_k(std::integral_constant<int, 3>{});      // (select_be_tile: k = 3 only)
+                else ok &= dispatch<1, 2, 3, 4>(k, launch_k);
+            });
+            return rc ? rc : ok ? check_launch("ffwm_block_extractor_backward(tile)") : no_kernel("ffwm_block_extractor_backward(tile)");
         }
     }
+    if (!pixels) return FFWM_OK;
     const Geometry g = plan(B, C, Hf, Wf, 32);
-#define FFWM_BE_BWD(KK)                                                                            \
-    case KK: {                                                                                     \
-        LaunchScope ls("block_extractor_bwd", st, bytes);                                          \
-        hipLaunchKernelGGL((be_bwd_kernel<T, KK>), dim3(g.grid), dim3(kBlock), 0, st, src, flow,   \
-                           gout, gsrc, gflow, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf,          \
-                           g.tiles_x, g.tiles_y, g.cslabs, g.cs, remap);                           \
-    } break;
-    const bool generic = options().be_bwd_variant == 9;
-    switch (generic ? 0 : k) {
-        FFWM_BE_BWD(1) FFWM_BE_BWD(2) FFWM_BE_BWD(3) FFWM_BE_BWD(4) FFWM_BE_BWD(5) FFWM_BE_BWD(6)
-        FFWM_BE_BWD(7)
-        default: {
-            const int64_t n = B * C * k * Hf * k * Wf;
-            const unsigned grid = static_cast<unsigned>(n / kBlock + 1 < 16384 ? n / kBlock + 1 : 16384);
-            LaunchScope ls("block_extractor_bwd_generic", st, bytes);
-            hipLaunchKernelGGL((be_bwd_generic<T>), dim3(grid), dim3(kBlock), 0, st, src, flow, gout,
-                               gsrc, gflow, n, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, k);
-        }
+    if (!generic) {
+        LaunchScope ls("block_extractor_bwd", st, bytes);
+        ok &= dispatch<1, 2, 3, 4, 5, 6, 7>(k, [&](auto K) {
+            hipLaunchKernelGGL((be_bwd_kernel<T, K.value>), dim3(g.grid), dim3(kBlock), 0, st, src, flow, gout, gsrc_px, gflow, (int)C, (int)Hs,
+                               (int)Ws, (int)Hf, (int)Wf, g.tiles_x, g.tiles_y, g.cslabs, g.cs, remap);
+        });
+    } else {
+        const int64_t n = B * C * k * Hf * k * Wf;
+        LaunchScope ls("block_extractor_bwd_generic", st, bytes);
+        hipLaunchKernelGGL((be_bwd_generic<T>), dim3(element_grid(n, 16384)), dim3(kBlock), 0, st, src, flow, gout,
+                           gsrc_px, gflow, n, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, k);
     }
-#undef FFWM_BE_BWD
-    return check_launch("ffwm_block_extractor_backward");
+    return ok ? check_launch("ffwm_block_extractor_backward") : no_kernel("ffwm_block_extractor_backward");
 }
 
 int check_dims(const char* fn, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf,
@@ -2846,54 +2847,73 @@ ba_fwd_pix_kernel(const float* __restrict__ src, const float* __restrict__ flow,
     }
 }
 
+// Configurations of the block-attention pixel kernels ba_fwd_pix_kernel / ba_bwd_pix_kernel<TH, CG, WPE>: tiles of 64 x TH pixels,
+// CG channels per group, WPE resident blocks per CU.  The option value is the position in the list (a value past the end: the first).
+template <int TH_, int CG_, int WPE_>
+struct BaPix {
+    static constexpr int TH = TH_, CG = CG_, WPE = WPE_;
+};
+template <class F>
+void select_ba_fwd_pix(int ba_fwd_pix, F&& f) {       // (0 = not this kernel: see launch_attn_fwd)
+    select<BaPix<8, 4, 4>, BaPix<8, 4, 4>, BaPix<16, 4, 4>, BaPix<8, 8, 4>, BaPix<8, 4, 6>>(ba_fwd_pix, f);
+}
+template <class F>
+void select_ba_bwd_pix(int ba_bwd_pix, F&& f) {
+    select<BaPix<16, 4, 3>, BaPix<8, 8, 4>, BaPix<16, 4, 4>, BaPix<16, 8, 3>, BaPix<8, 4, 4>, BaPix<8, 4, 6>>(ba_bwd_pix, f);
+}
+// ba_bwd_fused -> ba_bwd_src_kernel<TH, THREADS, 4>: tile rows / threads of a block (1 and every other value: 32 / 256)
+template <int TH_, int THREADS_>
+struct BaSrc {
+    static constexpr int TH = TH_, THREADS = THREADS_;
+};
+template <class F>
+void select_ba_bwd_src(int ba_bwd_fused, F&& f) {
+    select<BaSrc<32, 256>, BaSrc<32, 256>, BaSrc<16, 256>, BaSrc<32, 512>>(ba_bwd_fused, f);
+}
+
 template <typename T>
 int launch_attn_fwd(const T* src, const T* flow, const T* wts, T* out, int64_t B, int64_t C, int64_t Hs, int64_t Ws,
                     int64_t Hf, int64_t Wf, int k, hipStream_t st) {
     const double bytes = sizeof(T) * static_cast<double>(B) * (C * Hs * Ws + (2.0 + k * k) * Hf * Wf + static_cast<double>(C) * Hf * Wf);
+    const int remap = options().xcd_remap;
     if constexpr (sizeof(T) == 4) {
-        if (k == 3 && options().be_fwd_variant != 9 && options().ba_fwd_pix != 0 && Hs * Ws < (1LL << 29)) {
-            const int fm = options().ba_fwd_pix;                                       // 1: 64 x 8 pixels, 4 channels per group; 2: 64 x 16, 4; 3: 64 x 8, 8; 4: 64 x 8, 4, 6 blocks per CU
-            const int tha = fm == 2 ? 16 : 8, cga = fm == 3 ? 8 : 4, wpe = fm == 4 ? 6 : 4;
-            const int ntx = static_cast<int>((Wf + kTileRW - 1) / kTileRW), ntya = static_cast<int>((Hf + tha - 1) / tha);
-            const int64_t tiles = B * ntx * ntya;
-            int64_t want = (static_cast<int64_t>(wpe) * device_cus() + tiles - 1) / tiles;                   // slabs: one resident round of blocks
-            if (want < 1) want = 1;
-            int csa = static_cast<int>((C + want - 1) / want);
-            csa = (csa + cga - 1) / cga * cga;
-            while (csa > cga && static_cast<int64_t>(csa) * Hf * Wf * 4 >= (1LL << 31)) csa -= cga;       // 32-bit byte offsets over a slab of the output
-            const int slabsa = static_cast<int>((C + csa - 1) / csa);
-            FFWM_REQUIRE(tiles * slabsa < (1LL << 31), FFWM_ERR_SIZE, "ffwm_block_attention_forward: grid too large");
-            LaunchScope ls("block_attention_fwd_lds", st, bytes);
-#define FFWM_BA_FWD(TH_, CG_, WPE_)                                                                                                             \
-    hipLaunchKernelGGL((ba_fwd_pix_kernel<TH_, CG_, WPE_>), dim3(static_cast<unsigned>(tiles * slabsa)), dim3(kBlock), 0, st, src, flow, wts, out, \
-                       (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, ntx, ntya, slabsa, csa, options().xcd_remap)
-            if (fm == 2) FFWM_BA_FWD(16, 4, 4);
-            else if (fm == 3) FFWM_BA_FWD(8, 8, 4);
-            else if (fm == 4) FFWM_BA_FWD(8, 4, 6);
-            else FFWM_BA_FWD(8, 4, 4);
-#undef FFWM_BA_FWD
-            return check_launch("ffwm_block_attention_forward");
+        const bool fast = k == 3 && options().be_fwd_variant != 9;
+        const int pix = options().ba_fwd_pix;
+        if (fast && pix != 0 && Hs * Ws < (1LL << 29)) {
+            int rc = FFWM_OK;
+            select_ba_fwd_pix(pix, [&](auto cfg) {
+                using Cfg = decltype(cfg);
+                const int ntx = static_cast<int>((Wf + kTileRW - 1) / kTileRW), nty = static_cast<int>((Hf + Cfg::TH - 1) / Cfg::TH);
+                const int64_t tiles = B * ntx * nty;
+                const int cs = slab_for_residency(C, tiles, Cfg::WPE, Cfg::CG, Hf * Wf);       // 32-bit byte offsets over a slab of the output
+                const int cslabs = static_cast<int>((C + cs - 1) / cs);
+                if (tiles * cslabs >= (1LL << 31)) {
+                    set_error("ffwm_block_attention_forward: grid too large");
+                    rc = FFWM_ERR_SIZE;
+                    return;
+                }
+                LaunchScope ls("block_attention_fwd_lds", st, bytes);
+                hipLaunchKernelGGL((ba_fwd_pix_kernel<Cfg::TH, Cfg::CG, Cfg::WPE>), dim3(static_cast<unsigned>(tiles * cslabs)), dim3(kBlock), 0, st,
+                                   src, flow, wts, out, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, ntx, nty, cslabs, cs, remap);
+            });
+            return rc ? rc : check_launch("ffwm_block_attention_forward");
         }
-        if (k == 3 && options().be_fwd_variant != 9) {
+        if (fast) {      // rounds 3-5's be_fwd_lds_kernel<.., MODE 1>
             const Geometry g = plan(B, C, Hf, Wf, 16);
-            const int rpt = Hf >= 64 ? 4 : 1;
-            const int th = (kBlock / kWave) * rpt;
-            const int tyl = static_cast<int>((Hf + th - 1) / th);
-            const unsigned gridl = static_cast<unsigned>(B * g.tiles_x * tyl * g.cslabs);
             LaunchScope ls("block_attention_fwd_lds", st, bytes);
-            if (rpt == 4)
-                hipLaunchKernelGGL((be_fwd_lds_kernel<float, 3, 4, 1>), dim3(gridl), dim3(kBlock), 0, st, src, flow, out, (int)C,
-                                   (int)Hs, (int)Ws, (int)Hf, (int)Wf, g.tiles_x, tyl, g.cslabs, g.cs, options().xcd_remap, 0, wts);
-            else
-                hipLaunchKernelGGL((be_fwd_lds_kernel<float, 3, 1, 1>), dim3(gridl), dim3(kBlock), 0, st, src, flow, out, (int)C,
-                                   (int)Hs, (int)Ws, (int)Hf, (int)Wf, g.tiles_x, tyl, g.cslabs, g.cs, options().xcd_remap, 0, wts);
+            dispatch<4, 1>(Hf >= 64 ? 4 : 1, [&](auto RPT) {
+                constexpr int TH = (kBlock / kWave) * RPT.value;
+                const int tyl = static_cast<int>((Hf + TH - 1) / TH);
+                const unsigned gridl = static_cast<unsigned>(B * g.tiles_x * tyl * g.cslabs);
+                hipLaunchKernelGGL((be_fwd_lds_kernel<float, 3, RPT.value, 1>), dim3(gridl), dim3(kBlock), 0, st, src, flow, out, (int)C,
+                                   (int)Hs, (int)Ws, (int)Hf, (int)Wf, g.tiles_x, tyl, g.cslabs, g.cs, remap, 0, wts);
+            });
             return check_launch("ffwm_block_attention_forward");
         }
     }
     const int64_t n = B * C * Hf * Wf;
-    const unsigned grid = static_cast<unsigned>(n / kBlock + 1 < 65536 ? n / kBlock + 1 : 65536);
     LaunchScope ls("block_attention_fwd_generic", st, bytes);
-    hipLaunchKernelGGL((ba_fwd_generic<T>), dim3(grid), dim3(kBlock), 0, st, src, flow, wts, out, n, (int)C, (int)Hs, (int)Ws,
+    hipLaunchKernelGGL((ba_fwd_generic<T>), dim3(element_grid(n, 65536)), dim3(kBlock), 0, st, src, flow, wts, out, n, (int)C, (int)Hs, (int)Ws,
                        (int)Hf, (int)Wf, k);
     return check_launch("ffwm_block_attention_forward");
 }
@@ -2902,72 +2922,56 @@ template <typename T>
 int launch_attn_bwd(const T* src, const T* flow, const T* wts, const T* gout, T* gsrc, T* gflow, T* gw, int64_t B,
                     int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, int k, hipStream_t st) {
     const double bytes = sizeof(T) * static_cast<double>(B) * (static_cast<double>(C) * Hf * Wf + 2.0 * C * Hs * Ws + (4.0 + k * k) * Hf * Wf);
+    const int remap = options().xcd_remap;
     if constexpr (sizeof(T) == 4) {
         if (k == 3 && options().be_bwd_variant != 9 && Hs * Ws < (1LL << 29)) {
-            const int mode = options().ba_bwd_fused;
-            const int th = mode == 2 ? 16 : 32;
-            const int nts = mode == 3 ? 512 : 256;
-            constexpr int csf = 4;
-            const TileGeo geo{kTileRW, th, 4, th};
-            const int ntx = static_cast<int>((Wf + kTileRW - 1) / kTileRW), nty = static_cast<int>((Hf + th - 1) / th);
-            const int cslabs = static_cast<int>((C + csf - 1) / csf);
-            const Geometry gf = plan(B, C, Hf, Wf, 32);
-            if (gsrc) {                          // (the two halves are independent: a call that wants only d(flow) / d(weights) runs the pixel kernel alone)
-            {
-                LaunchScope ls("block_attention_bwd_far", st, sizeof(T) * 2.0 * B * Hf * Wf);
-                hipLaunchKernelGGL((be_bwd_far2_kernel<float, 3, true>), dim3(gf.grid), dim3(kBlock), 0, st, flow, gout, gsrc,
-                                   (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, gf.tiles_x, gf.tiles_y, gf.cslabs, gf.cs, geo, wts);
-            }
-            if (int rc = check_launch("ffwm_block_attention_backward(far)")) return rc;
-            FFWM_REQUIRE(B * ntx * nty * static_cast<int64_t>(cslabs) < (1LL << 31), FFWM_ERR_SIZE, "ffwm_block_attention_backward: grid too large");
-            {
-                const unsigned grid = static_cast<unsigned>(B * ntx * nty * cslabs);
-                LaunchScope ls("block_attention_bwd_src", st, bytes);        // (the OPERATOR's algorithmic bytes: bench.py prices the sum of the three scopes' times against them)
-#define FFWM_BA_SRC(TH_, NT_)                                                                                                  \
-    hipLaunchKernelGGL((ba_bwd_src_kernel<TH_, NT_, csf>), dim3(grid), dim3(NT_), 0, st, flow, wts, gout, gsrc, (int)C, (int)Hs, \
-                       (int)Ws, (int)Hf, (int)Wf, ntx, nty, cslabs, options().xcd_remap)
-                if (th == 16) FFWM_BA_SRC(16, 256);
-                else if (nts == 512) FFWM_BA_SRC(32, 512);
-                else FFWM_BA_SRC(32, 256);
-#undef FFWM_BA_SRC
-            }
-            if (int rc = check_launch("ffwm_block_attention_backward(source)")) return rc;
-            }
-            if (gflow || gw) {
-                // d(flow), d(weights): as many channels per block as still give every CU its resident blocks
-                const int cga = options().ba_bwd_pix == 1 || options().ba_bwd_pix == 3 ? 8 : 4;
-                const int pm = options().ba_bwd_pix;                                   // (common.hpp)
-                const int tha = pm == 1 || pm >= 4 ? 8 : 16;
-                const int ntya = static_cast<int>((Hf + tha - 1) / tha);
-                const int64_t tiles = B * ntx * ntya;
-                const int wpe = pm == 5 ? 6 : ((pm == 0 || pm == 3) ? 3 : 4);   // resident blocks per CU
-                int64_t want = (static_cast<int64_t>(wpe) * device_cus() + tiles - 1) / tiles;               // slabs: one resident round of blocks
-                if (want < 1) want = 1;
-                int csa = static_cast<int>((C + want - 1) / want);
-                csa = (csa + cga - 1) / cga * cga;
-                while (csa > cga && static_cast<int64_t>(csa) * Hf * Wf * 4 >= (1LL << 31)) csa -= cga;       // 32-bit byte offsets over a slab of grad_output
-                const int slabsa = static_cast<int>((C + csa - 1) / csa);
-                const unsigned grid = static_cast<unsigned>(tiles * slabsa);
+            // the two halves are independent: a call that wants only d(flow) / d(weights) runs the pixel kernel alone
+            const int ntx = static_cast<int>((Wf + kTileRW - 1) / kTileRW);
+            int rc = FFWM_OK;
+            if (gsrc) select_ba_bwd_src(options().ba_bwd_fused, [&](auto cfg) {
+                using Cfg = decltype(cfg);
+                constexpr int CS = 4;
+                constexpr TileGeo geo{kTileRW, Cfg::TH, 4, Cfg::TH};
+                const int nty = static_cast<int>((Hf + Cfg::TH - 1) / Cfg::TH);
+                const int cslabs = static_cast<int>((C + CS - 1) / CS);
+                const Geometry gf = plan(B, C, Hf, Wf, 32);
+                {
+                    LaunchScope ls("block_attention_bwd_far", st, sizeof(T) * 2.0 * B * Hf * Wf);
+                    hipLaunchKernelGGL((be_bwd_far2_kernel<float, 3, true>), dim3(gf.grid), dim3(kBlock), 0, st, flow, gout, gsrc,
+                                       (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, gf.tiles_x, gf.tiles_y, gf.cslabs, gf.cs, geo, wts);
+                }
+                if ((rc = check_launch("ffwm_block_attention_backward(far)"))) return;
+                if (B * ntx * nty * static_cast<int64_t>(cslabs) >= (1LL << 31)) {
+                    set_error("ffwm_block_attention_backward: grid too large");
+                    rc = FFWM_ERR_SIZE;
+                    return;
+                }
+                {
+                    const unsigned grid = static_cast<unsigned>(B * ntx * nty * cslabs);
+                    LaunchScope ls("block_attention_bwd_src", st, bytes);        // (the OPERATOR's algorithmic bytes: bench.py prices the sum of the three scopes' times against them)
+                    hipLaunchKernelGGL((ba_bwd_src_kernel<Cfg::TH, Cfg::THREADS, CS>), dim3(grid), dim3(Cfg::THREADS), 0, st, flow, wts, gout, gsrc,
+                                       (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, ntx, nty, cslabs, remap);
+                }
+                rc = check_launch("ffwm_block_attention_backward(source)");
+            });
+            if (rc || !(gflow || gw)) return rc;
+            // d(flow), d(weights): as many channels per block as still give every CU its resident blocks
+            select_ba_bwd_pix(options().ba_bwd_pix, [&](auto cfg) {
+                using Cfg = decltype(cfg);
+                const int nty = static_cast<int>((Hf + Cfg::TH - 1) / Cfg::TH);
+                const int64_t tiles = B * ntx * nty;
+                const int cs = slab_for_residency(C, tiles, Cfg::WPE, Cfg::CG, Hf * Wf);       // 32-bit byte offsets over a slab of grad_output
+                const int cslabs = static_cast<int>((C + cs - 1) / cs);
                 LaunchScope ls("block_attention_bwd_pix", st, sizeof(T) * static_cast<double>(B) * (static_cast<double>(C) * Hf * Wf + 1.0 * C * Hs * Ws + (4.0 + 2.0 * k * k) * Hf * Wf));
-#define FFWM_BA_PIX(TH_, CG_, WPE_)                                                                                                     \
-    hipLaunchKernelGGL((ba_bwd_pix_kernel<TH_, CG_, WPE_>), dim3(grid), dim3(kBlock), 0, st, src, flow, wts, gout, gflow, gw, (int)C, \
-                       (int)Hs, (int)Ws, (int)Hf, (int)Wf, ntx, ntya, slabsa, csa, options().xcd_remap)
-                if (pm == 1) FFWM_BA_PIX(8, 8, 4);
-                else if (pm == 2) FFWM_BA_PIX(16, 4, 4);
-                else if (pm == 3) FFWM_BA_PIX(16, 8, 3);
-                else if (pm == 4) FFWM_BA_PIX(8, 4, 4);
-                else if (pm == 5) FFWM_BA_PIX(8, 4, 6);
-                else FFWM_BA_PIX(16, 4, 3);
-#undef FFWM_BA_PIX
-                return check_launch("ffwm_block_attention_backward(pixels)");
-            }
-            return FFWM_OK;
+                hipLaunchKernelGGL((ba_bwd_pix_kernel<Cfg::TH, Cfg::CG, Cfg::WPE>), dim3(static_cast<unsigned>(tiles * cslabs)), dim3(kBlock), 0, st,
+                                   src, flow, wts, gout, gflow, gw, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, ntx, nty, cslabs, cs, remap);
+            });
+            return check_launch("ffwm_block_attention_backward(pixels)");
         }
     }
     const int64_t n = B * C * Hf * Wf;
-    const unsigned grid = static_cast<unsigned>(n / kBlock + 1 < 65536 ? n / kBlock + 1 : 65536);
     LaunchScope ls("block_attention_bwd_generic", st, bytes);
-    hipLaunchKernelGGL((ba_bwd_generic<T>), dim3(grid), dim3(kBlock), 0, st, src, flow, wts, gout, gsrc, gflow, gw, n, (int)C,
+    hipLaunchKernelGGL((ba_bwd_generic<T>), dim3(element_grid(n, 65536)), dim3(kBlock), 0, st, src, flow, wts, gout, gsrc, gflow, gw, n, (int)C,
                        (int)Hs, (int)Ws, (int)Hf, (int)Wf, k);
     return check_launch("ffwm_block_attention_backward");
 }
@@ -2983,12 +2987,10 @@ extern "C" int ffwm_block_extractor_forward(const void* source, const void* flow
     const char* fn = "ffwm_block_extractor_forward";
     FFWM_REQUIRE(source && flow_field && output, FFWM_ERR_ARG, "%s: NULL tensor pointer", fn);
     if (int rc = check_dims(fn, B, C, Hs, Ws, Hf, Wf, kernel_size, dtype)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == FFWM_F32)
-        return launch_fwd<float>((const float*)source, (const float*)flow_field, (float*)output, B, C,
-                                 Hs, Ws, Hf, Wf, kernel_size, st);
-    return launch_fwd<double>((const double*)source, (const double*)flow_field, (double*)output, B, C,
-                              Hs, Ws, Hf, Wf, kernel_size, st);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_fwd<T>((const T*)source, (const T*)flow_field, (T*)output, B, C, Hs, Ws, Hf, Wf, kernel_size, static_cast<hipStream_t>(stream));
+    });
 }
 
 extern "C" int ffwm_block_extractor_backward(const void* source, const void* flow_field,
@@ -3000,14 +3002,11 @@ extern "C" int ffwm_block_extractor_backward(const void* source, const void* flo
     FFWM_REQUIRE(source && flow_field && grad_output, FFWM_ERR_ARG, "%s: NULL tensor pointer", fn);
     if (int rc = check_dims(fn, B, C, Hs, Ws, Hf, Wf, kernel_size, dtype)) return rc;
     if (!grad_source && !grad_flow_field) return FFWM_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == FFWM_F32)
-        return launch_bwd<float>((const float*)source, (const float*)flow_field, (const float*)grad_output,
-                                 (float*)grad_source, (float*)grad_flow_field, B, C, Hs, Ws, Hf, Wf,
-                                 kernel_size, st);
-    return launch_bwd<double>((const double*)source, (const double*)flow_field, (const double*)grad_output,
-                              (double*)grad_source, (double*)grad_flow_field, B, C, Hs, Ws, Hf, Wf,
-                              kernel_size, st);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_bwd<T>((const T*)source, (const T*)flow_field, (const T*)grad_output, (T*)grad_source, (T*)grad_flow_field, B, C, Hs, Ws,
+                             Hf, Wf, kernel_size, static_cast<hipStream_t>(stream));
+    });
 }
 
 // grad_output read through its element strides (NULL / contiguous strides: the entry point above).  A strided grad_output -- autograd
@@ -3018,13 +3017,12 @@ template <typename T>
 int launch_bwd_strided(const T* src, const T* flow, const T* gout, T* gsrc, T* gflow, int64_t B, int64_t C, int64_t Hs, int64_t Ws,
                        int64_t Hf, int64_t Wf, int k, const int64_t* st4, hipStream_t st) {
     const int64_t n = B * C * k * Hf * k * Wf;
-    const unsigned grid = static_cast<unsigned>(n / kBlock + 1 < 16384 ? n / kBlock + 1 : 16384);
     const double bytes = sizeof(T) * static_cast<double>(B) * (static_cast<double>(C) * k * k * Hf * Wf + 2.0 * C * Hs * Ws + 4.0 * Hf * Wf);
     LaunchScope ls("block_extractor_bwd_strided", st, bytes);
     // (x stride 0 is the kernel's "contiguous" mark: an expanded last dimension passes through a stride struct with x = 0 replaced below)
     FFWM_REQUIRE(st4[3] != 0 || k * Wf == 1, FFWM_ERR_ARG, "ffwm_block_extractor_backward_strided: a grad_output expanded along its last dimension (stride 0) is not supported");
-    hipLaunchKernelGGL((be_bwd_generic<T>), dim3(grid), dim3(kBlock), 0, st, src, flow, gout, gsrc, gflow, n, (int)C, (int)Hs, (int)Ws,
-                       (int)Hf, (int)Wf, k, GoStrides{st4[0], st4[1], st4[2], st4[3] != 0 ? st4[3] : 1});
+    hipLaunchKernelGGL((be_bwd_generic<T>), dim3(element_grid(n, 16384)), dim3(kBlock), 0, st, src, flow, gout, gsrc, gflow, n, (int)C, (int)Hs,
+                       (int)Ws, (int)Hf, (int)Wf, k, GoStrides{st4[0], st4[1], st4[2], st4[3] != 0 ? st4[3] : 1});
     return check_launch("ffwm_block_extractor_backward_strided");
 }
 
@@ -3041,12 +3039,11 @@ extern "C" int ffwm_block_extractor_backward_strided(const void* source, const v
     for (int d = 0; d < 4; ++d)
         FFWM_REQUIRE(grad_output_strides[d] >= 0, FFWM_ERR_ARG, "%s: negative strides are not supported", fn);
     if (!grad_source && !grad_flow_field) return FFWM_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == FFWM_F32)
-        return launch_bwd_strided<float>((const float*)source, (const float*)flow_field, (const float*)grad_output, (float*)grad_source,
-                                         (float*)grad_flow_field, B, C, Hs, Ws, Hf, Wf, kernel_size, grad_output_strides, st);
-    return launch_bwd_strided<double>((const double*)source, (const double*)flow_field, (const double*)grad_output, (double*)grad_source,
-                                      (double*)grad_flow_field, B, C, Hs, Ws, Hf, Wf, kernel_size, grad_output_strides, st);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_bwd_strided<T>((const T*)source, (const T*)flow_field, (const T*)grad_output, (T*)grad_source, (T*)grad_flow_field, B, C, Hs,
+                                     Ws, Hf, Wf, kernel_size, grad_output_strides, static_cast<hipStream_t>(stream));
+    });
 }
 
 extern "C" int ffwm_block_attention_forward(const void* source, const void* flow_field, const void* weights, void* output,
@@ -3055,12 +3052,11 @@ extern "C" int ffwm_block_attention_forward(const void* source, const void* flow
     const char* fn = "ffwm_block_attention_forward";
     FFWM_REQUIRE(source && flow_field && weights && output, FFWM_ERR_ARG, "%s: NULL tensor pointer", fn);
     if (int rc = check_dims(fn, B, C, Hs, Ws, Hf, Wf, kernel_size, dtype)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == FFWM_F32)
-        return launch_attn_fwd<float>((const float*)source, (const float*)flow_field, (const float*)weights, (float*)output,
-                                      B, C, Hs, Ws, Hf, Wf, kernel_size, st);
-    return launch_attn_fwd<double>((const double*)source, (const double*)flow_field, (const double*)weights,
-                                   (double*)output, B, C, Hs, Ws, Hf, Wf, kernel_size, st);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_attn_fwd<T>((const T*)source, (const T*)flow_field, (const T*)weights, (T*)output, B, C, Hs, Ws, Hf, Wf, kernel_size,
+                                  static_cast<hipStream_t>(stream));
+    });
 }
 
 extern "C" int ffwm_block_attention_backward(const void* source, const void* flow_field, const void* weights,
@@ -3071,12 +3067,9 @@ extern "C" int ffwm_block_attention_backward(const void* source, const void* flo
     FFWM_REQUIRE(source && flow_field && weights && grad_output, FFWM_ERR_ARG, "%s: NULL tensor pointer", fn);
     if (int rc = check_dims(fn, B, C, Hs, Ws, Hf, Wf, kernel_size, dtype)) return rc;
     if (!grad_source && !grad_flow_field && !grad_weights) return FFWM_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == FFWM_F32)
-        return launch_attn_bwd<float>((const float*)source, (const float*)flow_field, (const float*)weights,
-                                      (const float*)grad_output, (float*)grad_source, (float*)grad_flow_field,
-                                      (float*)grad_weights, B, C, Hs, Ws, Hf, Wf, kernel_size, st);
-    return launch_attn_bwd<double>((const double*)source, (const double*)flow_field, (const double*)weights,
-                                   (const double*)grad_output, (double*)grad_source, (double*)grad_flow_field,
-                                   (double*)grad_weights, B, C, Hs, Ws, Hf, Wf, kernel_size, st);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_attn_bwd<T>((const T*)source, (const T*)flow_field, (const T*)weights, (const T*)grad_output, (T*)grad_source,
+                                  (T*)grad_flow_field, (T*)grad_weights, B, C, Hs, Ws, Hf, Wf, kernel_size, static_cast<hipStream_t>(stream));
+    });
 }

@@ -1146,26 +1146,19 @@ rs_bwd1_tile_kernel(const float* __restrict__ in2, const float* __restrict__ gou
 // A group with a NaN / Inf gradient scatters its own-tile taps with global atomics behind a flush of zeros.
 // Weights: w_tap / sum = (wy / sum_y) (wx / sum_x) held as 4 + 4 factors per pixel (8 registers instead of 16): sum = sum_y sum_x up to
 // rounding (resample2d_kernel.cu:87 adds the 16 products), SAFE_DIV's zero case kept per factor.
-#ifndef FFWM_RS_OWN_THREADS
-#define FFWM_RS_OWN_THREADS 512
-#endif
-#ifndef FFWM_RS_OWN_LDSW
-#define FFWM_RS_OWN_LDSW 0          // 1: the per-pixel factors and origins in LDS instead of registers (one block per CU: use with 1024 threads)
-#endif
 template <int HALF>
 struct RsOwn {
     static constexpr int NT = 2 * HALF;
     static constexpr int D = 3;                    // |floor offset| served on the fast path
     static constexpr int M = D + HALF;             // margin of the pixel region around the owned tile
-#ifndef FFWM_RS_OWN_RH
-#define FFWM_RS_OWN_RH 48          // measured: 48 rows (6 pixels per lane) 705 / 981 us smooth / random, 64 rows (8 per lane: 16 more registers of per-pixel state, scratch in the add loop) 786 / 947
-#endif
-    static constexpr int RW = 64, RH = FFWM_RS_OWN_RH;         // pixel region of a block
+    // pixel region of a block.  Rows, measured: 48 (6 pixels per lane) 705 / 981 us smooth / random, 64 (8 per lane: 16 more registers of
+    // per-pixel state, scratch in the add loop) 786 / 947
+    static constexpr int RW = 64, RH = 48;
     static constexpr int OW = RW - 2 * M, OH = RH - 2 * M;
     static constexpr int NDUMP = 8;                // dump columns behind the tile's: where a tap COLUMN of another block's tile goes (never read)
     static constexpr int BP = 64;                  // box pitch: OW + NDUMP <= 64
     static constexpr int NCELL = BP * OH;
-    static constexpr int THREADS = FFWM_RS_OWN_THREADS, NW = THREADS / 64, PPT = RH / NW;
+    static constexpr int THREADS = 512, NW = THREADS / 64, PPT = RH / NW;
     static_assert(OW + NDUMP <= BP, "box pitch");
 };
 
@@ -1236,18 +1229,7 @@ rs_bwd1_owned_kernel(const float* __restrict__ in2, const float* __restrict__ go
     using G = RsOwn<HALF>;
     constexpr int NT = G::NT, M = G::M, OW = G::OW, OH = G::OH, BP = G::BP, NCELL = G::NCELL, NW = G::NW, PPT = G::PPT;
     constexpr unsigned kMagicBits = 0x4B400000u;   // 1.5 * 2^23
-#if FFWM_RS_OWN_LDSW
-    // [4 channels + the tap count][OH][BP], then the per-pixel state: 2 (NT - 1) factor planes + the packed origins, [plane][pixel] with
-    // pixel = r THREADS + thread (a wave reads 64 consecutive dwords: conflict-free).  One 16-wave block per CU, NO per-pixel registers.
-    extern __shared__ __attribute__((aligned(16))) unsigned char rs_own_smem[];
-    unsigned* const box = reinterpret_cast<unsigned*>(rs_own_smem);
-    float* const fac = reinterpret_cast<float*>(rs_own_smem) + 5 * NCELL;
-#define RS_WY(r, f) fac[((f) * PPT + (r)) * G::THREADS + threadIdx.x]
-#define RS_WX(r, f) fac[((NT - 1 + (f)) * PPT + (r)) * G::THREADS + threadIdx.x]
-#define RS_UV(r) reinterpret_cast<int*>(fac)[((2 * (NT - 1)) * PPT + (r)) * G::THREADS + threadIdx.x]
-#else
     __shared__ unsigned box[5 * NCELL];            // [4 channels + the tap count][OH][BP]
-#endif
     __shared__ unsigned redm[NW];
     __shared__ int redp[NW];
     unsigned* const cnt = box + 4 * NCELL;
@@ -1269,13 +1251,8 @@ rs_bwd1_owned_kernel(const float* __restrict__ in2, const float* __restrict__ go
     const float* fb = in2 + static_cast<size_t>(b) * 3 * plane;
     // the normalised factors of an axis sum to 1: NT - 1 of them are kept, the last one is 1 - the others (absolute error <= 2e-7,
     // the size of one fixed-point unit) -- 16 registers less per thread, which is what lets the add loop live in 128 without scratch
-#if !FFWM_RS_OWN_LDSW
     float wyn[PPT][NT - 1], wxn[PPT][NT - 1];
     int uv[PPT];                                   // (v0 - Y0) << 16 | (u0 - X0) & 0xffff, clamped to +-2048 (enough: see colx)
-#define RS_WY(r, f) wyn[r][f]
-#define RS_WX(r, f) wxn[r][f]
-#define RS_UV(r) uv[r]
-#endif
     unsigned livemask = 0;
 #pragma unroll
     for (int r = 0; r < PPT; ++r) {
@@ -1284,7 +1261,7 @@ rs_bwd1_owned_kernel(const float* __restrict__ in2, const float* __restrict__ go
         int u0 = 0, v0 = 0;
         bool ok = false;
 #pragma unroll
-        for (int f = 0; f < NT - 1; ++f) RS_WY(r, f) = RS_WX(r, f) = 0.f;
+        for (int f = 0; f < NT - 1; ++f) wyn[r][f] = wxn[r][f] = 0.f;
         bool degenerate = false;
         if (live_px) {
             const size_t poff = static_cast<size_t>(y) * W + x;
@@ -1293,7 +1270,7 @@ rs_bwd1_owned_kernel(const float* __restrict__ in2, const float* __restrict__ go
             if (ok) {
                 const RsFactors<HALF> fc = rs_pixel_factors<HALF>(dx, dy, sgm, x, y, Hi, Wi, quirk);
 #pragma unroll
-                for (int f = 0; f < NT - 1; ++f) { RS_WX(r, f) = fc.wx[f]; RS_WY(r, f) = fc.wy[f]; }
+                for (int f = 0; f < NT - 1; ++f) { wxn[r][f] = fc.wx[f]; wyn[r][f] = fc.wy[f]; }
                 degenerate = fc.degenerate != 0;
             }
         }
@@ -1302,7 +1279,7 @@ rs_bwd1_owned_kernel(const float* __restrict__ in2, const float* __restrict__ go
         // (a pixel that is dead here -- outside the flow grid, or irregular: the far kernel's -- is skipped through `livemask`)
         const int ur = on ? min(max(u0 - X0, -2048), 2048) : 0;
         const int vr = on ? min(max(v0 - Y0, -2048), 2048) : 0;
-        RS_UV(r) = (vr << 16) | (ur & 0xffff);
+        uv[r] = (vr << 16) | (ur & 0xffff);
         __builtin_amdgcn_sched_barrier(0);
     }
     // tile-relative column / row of tap f of a pixel with packed origin `o`: the reference's clamp to the image, then the test against
@@ -1321,9 +1298,9 @@ rs_bwd1_owned_kernel(const float* __restrict__ in2, const float* __restrict__ go
         int cx[NT], ry[NT];
 #pragma unroll
         for (int f = 0; f < NT; ++f) {
-            cx[f] = colx(RS_UV(r), f);
+            cx[f] = colx(uv[r], f);
             cx[f] = static_cast<unsigned>(cx[f]) < static_cast<unsigned>(OW) ? cx[f] : dumpc;
-            ry[f] = rowy(RS_UV(r), f);
+            ry[f] = rowy(uv[r], f);
         }
 #pragma unroll
         for (int pr = 0; pr < NT; ++pr) {
@@ -1424,13 +1401,13 @@ rs_bwd1_owned_kernel(const float* __restrict__ in2, const float* __restrict__ go
                 if (!((livemask >> r) & 1u)) continue;
                 // the pixel's origin and factors pass through an opaque register copy: everything derived from them (box offsets, 16
                 // weight products) is channel-invariant, and hipcc would hoist all of it out of the channel loop -- 24 registers per pixel
-                int o = RS_UV(r);
+                int o = uv[r];
                 asm volatile("" : "+v"(o));
                 float wy4[NT], wx4[NT];
                 float ry1 = 1.f, rx1 = 1.f;
 #pragma unroll
                 for (int f = 0; f < NT - 1; ++f) {
-                    wy4[f] = RS_WY(r, f); wx4[f] = RS_WX(r, f);
+                    wy4[f] = wyn[r][f]; wx4[f] = wxn[r][f];
                     asm volatile("" : "+v"(wy4[f]), "+v"(wx4[f]));
                     ry1 -= wy4[f]; rx1 -= wx4[f];
                 }
@@ -1564,9 +1541,6 @@ rs_bwd1_owned_kernel(const float* __restrict__ in2, const float* __restrict__ go
         c += 4;
     }
 }
-#undef RS_WY
-#undef RS_WX
-#undef RS_UV
 
 // The complement of rs_bwd1_owned_kernel: (pixel, tap) pairs whose pixel is not visited by the block that owns the tap's cell.
 template <int HALF>
@@ -2029,69 +2003,136 @@ int check_dims(const char* fn, int64_t B, int64_t C, int64_t Hi, int64_t Wi, int
     return FFWM_OK;
 }
 
-unsigned generic_grid(int64_t n) {
-    const int64_t blocks = (n + kBlock - 1) / kBlock;
-    return static_cast<unsigned>(blocks < 16384 ? blocks : 16384);
+unsigned generic_grid(int64_t n) { return capped_grid((n + kBlock - 1) / kBlock, 16384); }
+
+// Launch geometry of the tile kernels: tiles of tile_w x tile_h over a W x H plane, the channels cut into slabs of a multiple of 4
+// until the launch has `min_blocks` blocks (512: >= 2 blocks per CU).
+struct RsTiles {
+    int tiles_x, tiles_y, cs, cslabs;
+    unsigned grid;
+};
+inline RsTiles plan_tiles(int64_t B, int64_t C, int64_t H, int64_t W, int tile_w, int tile_h, int min_blocks = 512) {
+    RsTiles t;
+    t.tiles_x = static_cast<int>((W + tile_w - 1) / tile_w);
+    t.tiles_y = static_cast<int>((H + tile_h - 1) / tile_h);
+    const int64_t spatial = B * t.tiles_x * t.tiles_y;
+    t.cs = slab_of_fours(C, spatial, min_blocks);
+    t.cslabs = static_cast<int>((C + t.cs - 1) / t.cs);
+    t.grid = static_cast<unsigned>(spatial * t.cslabs);
+    return t;
 }
+
+// rs_fwd_variant -> the LDS-tile forward rs_fwd_lds_kernel<HALF, RPT, DB>: tiles of 64 x 4 RPT pixels (RPT 0 = by shape), two staging
+// buffers or one.  (1 = the direct-gather kernel: no entry of its own; a value beyond the table is "auto".)
+constexpr struct { int rpt; bool db; } kRsFwdLds[8] = {{0, true}, {0, true}, {4, true}, {1, true}, {2, true}, {2, false}, {4, false}, {1, false}};
 
 template <typename T>
 int launch_fwd(const T* in1, const T* in2, T* out, int64_t B, int64_t C, int64_t Hi, int64_t Wi,
                int64_t H, int64_t W, int ks, int dil, hipStream_t st) {
     const double bytes = sizeof(T) * static_cast<double>(B) * H * W * (2.0 * C + 3.0);
     const int remap = options().xcd_remap;
+    const int half = ks / 2;
+    const int v = options().rs_fwd_variant;
+    bool ok = true;          // false: a dispatch below found no kernel for its value
     if constexpr (sizeof(T) == 4) {
-        const int half = ks / 2;
-        if (dil == 1 && half >= 1 && half <= 3 && options().rs_fwd_variant != 1) {
-            // tile rows 4 * rpt; channels cut into slabs of a multiple of 4 until there are >= 2 blocks per CU
-            const int tiles_x = static_cast<int>((W + kTileX - 1) / kTileX);
-            const int v = options().rs_fwd_variant;
-            int rpt = (v == 2 || v == 6) ? 4 : (v == 3 || v == 7) ? 1 : (v == 4 || v == 5) ? 2
-                      : (B * tiles_x * ((H + 7) / 8) >= 2048 ? 2 : 1);      // measured: 64 x 8 tiles >= 64 x 16 > 64 x 4 at HBM-resident sizes
-            const bool db = !(v >= 5 && v <= 7);
-            const int tiles_y = static_cast<int>((H + 4 * rpt - 1) / (4 * rpt));
-            const int64_t spatial = B * tiles_x * tiles_y;
-            int cs = static_cast<int>((C + 3) / 4 * 4);
-            while (cs > 4 && spatial * ((C + cs - 1) / cs) < 512) cs = (cs / 2 + 3) / 4 * 4;
-            const int cslabs = static_cast<int>((C + cs - 1) / cs);
-            const unsigned grid = static_cast<unsigned>(spatial * cslabs);
-            const size_t lds = static_cast<size_t>(db ? 2 : 1) * (4 * rpt + 12) * kRsBoxW * 16;
+        if (dil == 1 && half >= 1 && half <= 3 && v != 1) {
+            const auto cfg = kRsFwdLds[v >= 0 && v < 8 ? v : 0];
+            // measured: 64 x 8 tiles >= 64 x 16 > 64 x 4 at HBM-resident sizes
+            const int rpt = cfg.rpt ? cfg.rpt : (B * ((W + kTileX - 1) / kTileX) * ((H + 7) / 8) >= 2048 ? 2 : 1);
             LaunchScope ls("resample2d_fwd_lds", st, bytes);
-#define FFWM_RS_FWD_LDS(HH, RR, DD)                                                                        \
-    do {                                                                                                   \
-        allow_large_lds(reinterpret_cast<const void*>(rs_fwd_lds_kernel<HH, RR, DD>));                     \
-        hipLaunchKernelGGL((rs_fwd_lds_kernel<HH, RR, DD>), dim3(grid), dim3(kBlock), lds, st, in1, in2, out, \
-                           (int)C, (int)Hi, (int)Wi, (int)H, (int)W, tiles_x, tiles_y, cslabs, cs, remap); \
-    } while (0)
-#define FFWM_RS_FWD_LDS_H(RR, DD)                                                                          \
-    do {                                                                                                   \
-        if (half == 1) FFWM_RS_FWD_LDS(1, RR, DD); else if (half == 2) FFWM_RS_FWD_LDS(2, RR, DD); else FFWM_RS_FWD_LDS(3, RR, DD); \
-    } while (0)
-            if (rpt == 4) { if (db) FFWM_RS_FWD_LDS_H(4, true); else FFWM_RS_FWD_LDS_H(4, false); }
-            else if (rpt == 2) { if (db) FFWM_RS_FWD_LDS_H(2, true); else FFWM_RS_FWD_LDS_H(2, false); }
-            else { if (db) FFWM_RS_FWD_LDS_H(1, true); else FFWM_RS_FWD_LDS_H(1, false); }
-#undef FFWM_RS_FWD_LDS_H
-#undef FFWM_RS_FWD_LDS
-            return check_launch("ffwm_resample2d_forward(lds)");
+            ok &= dispatch<1, 2, 3>(half, [&](auto HALF) {
+                return dispatch<4, 2, 1>(rpt, [&](auto RPT) {
+                    dispatch<true, false>(cfg.db, [&](auto DB) {
+                        constexpr int TH = 4 * RPT.value;
+                        const RsTiles t = plan_tiles(B, C, H, W, kTileX, TH);
+                        const size_t lds = static_cast<size_t>(DB.value ? 2 : 1) * (TH + 12) * kRsBoxW * 16;
+                        auto kfn = rs_fwd_lds_kernel<HALF.value, RPT.value, DB.value>;
+                        allow_large_lds(reinterpret_cast<const void*>(kfn));
+                        hipLaunchKernelGGL(kfn, dim3(t.grid), dim3(kBlock), lds, st, in1, in2, out, (int)C, (int)Hi, (int)Wi, (int)H, (int)W,
+                                           t.tiles_x, t.tiles_y, t.cslabs, t.cs, remap);
+                    });
+                });
+            });
+            return ok ? check_launch("ffwm_resample2d_forward(lds)") : no_kernel("ffwm_resample2d_forward(lds)");
         }
     }
     const Geometry g = plan(B, C, H, W, 16);
     LaunchScope ls("resample2d_fwd", st, bytes);
-#define FFWM_RS_FWD(HH)                                                                             \
-    case 2 * HH:                                                                                    \
-        hipLaunchKernelGGL((rs_fwd_kernel<T, HH>), dim3(g.grid), dim3(kBlock), 0, st, in1, in2, out, \
-                           (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, g.tiles_x, g.tiles_y,      \
-                           g.cslabs, g.cs, remap);                                                  \
-        break;
-    switch (ks & ~1) {
-        FFWM_RS_FWD(1) FFWM_RS_FWD(2) FFWM_RS_FWD(3)
-        default: {
-            const int64_t n = B * C * H * W;
-            hipLaunchKernelGGL((rs_fwd_generic<T>), dim3(generic_grid(n)), dim3(kBlock), 0, st, in1, in2,
-                               out, n, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, ks, dil);
-        }
+    const bool fast = dispatch<1, 2, 3>(half, [&](auto HALF) {
+        hipLaunchKernelGGL((rs_fwd_kernel<T, HALF.value>), dim3(g.grid), dim3(kBlock), 0, st, in1, in2, out, (int)C, (int)Hi, (int)Wi, (int)H,
+                           (int)W, dil, g.tiles_x, g.tiles_y, g.cslabs, g.cs, remap);
+    });
+    if (!fast) {
+        const int64_t n = B * C * H * W;
+        hipLaunchKernelGGL((rs_fwd_generic<T>), dim3(generic_grid(n)), dim3(kBlock), 0, st, in1, in2,
+                           out, n, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, ks, dil);
     }
-#undef FFWM_RS_FWD
     return check_launch("ffwm_resample2d_forward");
+}
+
+// Which kernels a backward call gets.  Decided once from the shape and the options (each read here and nowhere else); launch_bwd
+// launches what is set, in the order of the fields.
+struct BwdRoute {
+    // ---- d_input1: exactly one of owned / (taplane and / or tile) / plane / pixels when it is wanted
+    // Round 6: owned tiles (rs_bwd1_owned_kernel + rs_bwd1_far_kernel, plain stores) for the calls the shared-cell tile kernel served:
+    // fp32, dilation 1, kernel_size 2 / 4, >= 2^18 pixels, planes of >= 32 rows.  rs_bwd1_owned: 0 = on, 2 = off (rounds 3-5's kernels).
+    bool owned;
+    int owned_min_blocks;
+    bool clear1;           // every other path ACCUMULATES into grad_input1: an uninitialised buffer is cleared first
+    // ks = 4, large calls, rs_bwd1_fixed = 2: the tile kernel when the flow is smooth, the tap-lane kernel when it is not --
+    // rs_flow_irregular_kernel counts into `sel`, both are launched, one returns
+    bool adaptive;
+    int* sel;
+    // the tap-lane kernel (ks = 4, flow-independent): small calls; 4 waves x 2 rows = 64 x 8 pixel tiles, two blocks per CU (56 KB box +
+    // 22 KB staging each); rs_bwd1_variant 5: 8 waves x 2 rows (one block per CU, a quarter fewer fold atomics: measured 1.61 against
+    // 1.53 ms at [8,64,512,512])
+    bool taplane;
+    int taplane_waves;
+    // the shared-cell tile kernel: planes beyond LDS ([8,64,512,512]: 3.1 ms vs 57 ms with per-tap global atomics); alone for every large
+    // call (rs_bwd1_variant 6, and the default since its box holds fixed-point cells and no longer depends on the flow:
+    // [8,64,512,512] 1.23 ms random / 0.91 ms smooth against the adaptive pair's 1.58 / 0.98 -- profiles/r05_rs_bwd1_fixed_point_ab.txt)
+    bool tile;
+    int tile_rpt;          // pixel rows per thread: tiles of 64 x 4 rpt
+    bool tile_fixed;       // 32-bit fixed-point box cells (round 5); rs_bwd1_fixed = 2: double cells
+    // planes that fit LDS whole (measured, cfg-1: 36 vs 47 us; [8,64,128,128]: 218 vs 235 us); also fp64, dilation > 1, scatter_variant 2
+    bool plane;
+    bool pixels1;          // per-tap global atomics (scatter_variant 1, kernel_size > 6, planes beyond LDS off the fp32 path)
+    // ---- d_input2
+    bool in2_lds;          // fp32, dilation 1, kernel_size 2 / 4 / 6
+    bool in2_pixels;
+};
+inline BwdRoute route_bwd(bool want1, bool want2, bool uninitialised, size_t esz, int64_t B, int64_t Hi, int64_t Wi, int64_t H, int64_t W,
+                          int half, int dil, hipStream_t st) {
+    const Options& o = options();
+    const int variant = o.rs_bwd1_variant;
+    const size_t plane_lds = static_cast<size_t>(Hi) * Wi * sizeof(double);     // the LDS accumulator is double
+    // fp32, dilation 1, kernel_size 2 / 4 / 6: the LDS-tile kernels (scatter_variant 1 = global atomics, 2 = plane kernel)
+    const bool lds_tiles = esz == 4 && dil == 1 && half >= 1 && half <= 3 && o.scatter_variant == 0;
+    const bool large = B * H * W >= (1 << 18) && H >= 32;
+    BwdRoute r;
+    r.owned = want1 && lds_tiles && half <= 2 && variant == 0 && o.rs_bwd1_owned != 2 &&
+              B * H * W >= (o.rs_bwd1_owned_min_pixels > 0 ? o.rs_bwd1_owned_min_pixels : (1 << 18)) && H >= 32 && Hi >= 32 &&
+              Hi * Wi < (1LL << 29) && H * W < (1LL << 29);
+    // a block pays ~15 us for its pixels' weights (double-precision exponentials) and the population count before its first channel:
+    // slabs as large as two rounds of the 512 resident blocks allow ([8,64,512,512], 800 tiles: 32 channels 722 us, 16: 815, 8: 907)
+    r.owned_min_blocks = o.rs_bwd1_owned_blocks > 0 ? o.rs_bwd1_owned_blocks : 1024;
+    const bool rest1 = want1 && !r.owned;
+    r.clear1 = uninitialised && rest1;
+    r.tile_fixed = o.rs_bwd1_fixed != 2;
+    r.tile_rpt = H >= 32 ? (o.rs_bwd1_rpt == 2 ? 2 : 4) : 1;
+    const bool tiles1 = rest1 && lds_tiles;
+    const bool tile_only = tiles1 && (variant == 6 || (variant == 0 && r.tile_fixed)) && large;
+    r.sel = tiles1 && half == 2 && variant == 0 && !tile_only && large ? static_cast<int*>(stream_scratch(st)) : nullptr;
+    r.adaptive = r.sel != nullptr;
+    r.taplane = tiles1 && half == 2 && (variant == 0 || variant == 5) && !tile_only;
+    r.taplane_waves = variant == 5 ? 8 : 4;
+    r.tile = tiles1 && (r.adaptive || tile_only || (!r.taplane && (plane_lds > 131072 || variant == 2)));
+    const bool left1 = rest1 && !r.taplane && !r.tile;
+    r.plane = left1 && plane_lds <= 131072 && half >= 1 && half <= 3 && o.scatter_variant != 1;
+    r.pixels1 = left1 && !r.plane;
+    r.in2_lds = want2 && lds_tiles;
+    r.in2_pixels = want2 && !r.in2_lds;
+    return r;
 }
 
 template <typename T>
@@ -2099,248 +2140,146 @@ int launch_bwd(const T* in1, const T* in2, const T* gout, T* gin1, T* gin2, int6
                int64_t Hi, int64_t Wi, int64_t H, int64_t W, int ks, int dil, int quirk_flags,
                hipStream_t st) {
     const int remap = options().xcd_remap;
-    const size_t plane_lds = static_cast<size_t>(Hi) * Wi * sizeof(double);     // the LDS accumulator is double
     const int half = ks / 2;
     const int quirk = quirk_flags & 1;
     const bool overwrite = (quirk_flags & 2) != 0 && gin1 != nullptr;           // grad_input1 arrives uninitialised
+    const BwdRoute r = route_bwd(gin1 != nullptr, gin2 != nullptr, overwrite, sizeof(T), B, Hi, Wi, H, W, half, dil, st);
+    const double bytes1 = sizeof(T) * static_cast<double>(B) * (C * (static_cast<double>(H) * W + 2.0 * Hi * Wi) + 3.0 * H * W);
+    const double bytes2 = sizeof(T) * static_cast<double>(B) * H * W * (2.0 * C + 6.0);
+    bool ok = true;          // false: a dispatch below found no kernel for its value
     if constexpr (sizeof(T) == 4) {
-        // Round 6: owned tiles (rs_bwd1_owned_kernel + rs_bwd1_far_kernel) for the calls the shared-cell tile kernel served: fp32, dilation 1,
-        // kernel_size 2 / 4, >= 2^18 pixels, planes of >= 32 rows.  rs_bwd1_owned: 0 = on, 2 = off (rounds 3-5's kernels).
-        if (gin1 && dil == 1 && (half == 1 || half == 2) && options().scatter_variant == 0 && options().rs_bwd1_variant == 0 &&
-            options().rs_bwd1_owned != 2 && B * H * W >= (options().rs_bwd1_owned_min_pixels > 0 ? options().rs_bwd1_owned_min_pixels : (1 << 18)) && H >= 32 && Hi >= 32 &&
-            static_cast<int64_t>(Hi) * Wi < (1LL << 29) && static_cast<int64_t>(H) * W < (1LL << 29)) {
-            const double bytes1 = sizeof(T) * static_cast<double>(B) * (C * (static_cast<double>(H) * W + 2.0 * Hi * Wi) + 3.0 * H * W);
-            const int ow = half == 1 ? RsOwn<1>::OW : RsOwn<2>::OW, oh = half == 1 ? RsOwn<1>::OH : RsOwn<2>::OH;
-            const int tiles_x = static_cast<int>((Wi + ow - 1) / ow), tiles_y = static_cast<int>((Hi + oh - 1) / oh);
-            const int64_t spatial = B * tiles_x * tiles_y;
-            int cs = static_cast<int>((C + 3) / 4 * 4);
-            // a block pays ~15 us for its pixels' weights (double-precision exponentials) and the population count before its first channel:
-            // slabs as large as two rounds of the 512 resident blocks allow ([8,64,512,512], 800 tiles: 32 channels 722 us, 16: 815, 8: 907)
-            const int min_blocks = options().rs_bwd1_owned_blocks > 0 ? options().rs_bwd1_owned_blocks : 1024;
-            while (cs > 4 && spatial * ((C + cs - 1) / cs) < min_blocks) cs = (cs / 2 + 3) / 4 * 4;
-            const int cslabs = static_cast<int>((C + cs - 1) / cs);
+        if (r.owned) {
             LaunchScope ls("resample2d_bwd_input1_owned", st, bytes1);      // both launches: the tiles and their far complement
-            {
-                const unsigned grid = static_cast<unsigned>(spatial * cslabs);
-#if FFWM_RS_OWN_LDSW
-                const size_t lds1 = 4u * (5u * RsOwn<1>::NCELL + (2u * (RsOwn<1>::NT - 1) + 1u) * RsOwn<1>::PPT * RsOwn<1>::THREADS);
-                const size_t lds2 = 4u * (5u * RsOwn<2>::NCELL + (2u * (RsOwn<2>::NT - 1) + 1u) * RsOwn<2>::PPT * RsOwn<2>::THREADS);
-                allow_large_lds(reinterpret_cast<const void*>(rs_bwd1_owned_kernel<1>));
-                allow_large_lds(reinterpret_cast<const void*>(rs_bwd1_owned_kernel<2>));
-#else
-                const size_t lds1 = 0, lds2 = 0;
-#endif
-                if (half == 1)
-                    hipLaunchKernelGGL((rs_bwd1_owned_kernel<1>), dim3(grid), dim3(RsOwn<1>::THREADS), lds1, st, (const float*)in2, (const float*)gout,
-                                       (float*)gin1, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, quirk, overwrite ? 1 : 0, tiles_x, tiles_y, cslabs, cs, remap);
-                else
-                    hipLaunchKernelGGL((rs_bwd1_owned_kernel<2>), dim3(grid), dim3(RsOwn<2>::THREADS), lds2, st, (const float*)in2, (const float*)gout,
-                                       (float*)gin1, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, quirk, overwrite ? 1 : 0, tiles_x, tiles_y, cslabs, cs, remap);
-            }
-            if (int rc = check_launch("ffwm_resample2d_backward(input1, owned tiles)")) return rc;
-            {
-                // one thread per pixel with ALL channels: for a flow net's field the launch reads the flow and returns
-                const Geometry gf = plan(B, C, H, W, static_cast<int>(C));
-                if (half == 1)
-                    hipLaunchKernelGGL((rs_bwd1_far_kernel<1>), dim3(gf.grid), dim3(kBlock), 0, st, (const float*)in2, (const float*)gout, (float*)gin1,
-                                       (int)C, (int)Hi, (int)Wi, (int)H, (int)W, quirk, gf.tiles_x, gf.tiles_y, gf.cslabs, gf.cs);
-                else
-                    hipLaunchKernelGGL((rs_bwd1_far_kernel<2>), dim3(gf.grid), dim3(kBlock), 0, st, (const float*)in2, (const float*)gout, (float*)gin1,
-                                       (int)C, (int)Hi, (int)Wi, (int)H, (int)W, quirk, gf.tiles_x, gf.tiles_y, gf.cslabs, gf.cs);
-            }
-            if (int rc = check_launch("ffwm_resample2d_backward(input1, far)")) return rc;
-            if (!gin2) return FFWM_OK;
-            gin1 = nullptr;
+            ok &= dispatch<1, 2>(half, [&](auto HALF) {
+                using G = RsOwn<HALF.value>;
+                const RsTiles t = plan_tiles(B, C, Hi, Wi, G::OW, G::OH, r.owned_min_blocks);
+                hipLaunchKernelGGL((rs_bwd1_owned_kernel<HALF.value>), dim3(t.grid), dim3(G::THREADS), 0, st, (const float*)in2, (const float*)gout,
+                                   (float*)gin1, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, quirk, overwrite ? 1 : 0, t.tiles_x, t.tiles_y, t.cslabs,
+                                   t.cs, remap);
+            });
+            if (int rc = ok ? check_launch("ffwm_resample2d_backward(input1, owned tiles)") : no_kernel("ffwm_resample2d_backward(input1, owned tiles)")) return rc;
+            // one thread per pixel with ALL channels: for a flow net's field the launch reads the flow and returns
+            const Geometry gf = plan(B, C, H, W, static_cast<int>(C));
+            ok &= dispatch<1, 2>(half, [&](auto HALF) {
+                hipLaunchKernelGGL((rs_bwd1_far_kernel<HALF.value>), dim3(gf.grid), dim3(kBlock), 0, st, (const float*)in2, (const float*)gout,
+                                   (float*)gin1, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, quirk, gf.tiles_x, gf.tiles_y, gf.cslabs, gf.cs);
+            });
+            if (int rc = ok ? check_launch("ffwm_resample2d_backward(input1, far)") : no_kernel("ffwm_resample2d_backward(input1, far)")) return rc;
         }
     }
-    // every other path ACCUMULATES into grad_input1: an uninitialised buffer is cleared here
-    if (overwrite && gin1)
+    if (r.clear1)
         if (zero_fill(gin1, sizeof(T) * static_cast<size_t>(B) * C * Hi * Wi, st)) return FFWM_ERR_LAUNCH;
     if constexpr (sizeof(T) == 4) {
-        // fp32, dilation 1, kernel_size 2 / 4 / 6: the LDS-tile kernels (scatter_variant 1 = global atomics, 2 = plane kernel)
-        if (dil == 1 && half >= 1 && half <= 3 && options().scatter_variant == 0) {
-            const int tiles_x = static_cast<int>((W + kTileX - 1) / kTileX);
-            auto slabs = [&](int64_t spatial, int& cs, int& cslabs) {
-                cs = static_cast<int>((C + 3) / 4 * 4);
-                while (cs > 4 && spatial * ((C + cs - 1) / cs) < 512) cs = (cs / 2 + 3) / 4 * 4;
-                cslabs = static_cast<int>((C + cs - 1) / cs);
-            };
-            // d_input1: planes that fit LDS whole keep the plane kernel below (measured, cfg-1: 36 vs 47 us; [8,64,128,128]: 218 vs
-            // 235 us); larger planes take the tile kernel ([8,64,512,512]: 3.1 ms vs 57 ms with per-tap global atomics)
-            // d_input1, ks = 4.  Small calls: the tap-lane kernel (flow-independent).  Large calls (>= 2^18 pixels): the tile kernel when
-            // the flow is smooth, the tap-lane kernel when it is not -- rs_flow_irregular_kernel counts, both are launched, one returns.
-            const int variant = options().rs_bwd1_variant;
-            int* sel = nullptr;
-            int sel_limit = 0;
-            // (round 5) variant 6: the tile kernel alone for every large call -- with fixed-point cells it no longer depends on the flow
-            // (the default since the box holds fixed-point cells: [8,64,512,512] 1.23 ms random / 0.91 ms smooth against the adaptive
-            // pair's 1.58 / 0.98 -- profiles/r05_rs_bwd1_fixed_point_ab.txt; rs_bwd1_fixed = 2 brings the pair of rounds 3-4 back)
-            const bool tile_only = gin1 && (variant == 6 || (variant == 0 && options().rs_bwd1_fixed != 2)) && B * H * W >= (1 << 18) && H >= 32;
-            bool adaptive = gin1 && half == 2 && variant == 0 && !tile_only && B * H * W >= (1 << 18) && H >= 32;
-            if (adaptive) {
-                sel = static_cast<int*>(stream_scratch(st));
-                adaptive = sel != nullptr;
-            }
-            // one profiling scope over the whole sequence of an adaptive call (pre-pass + the kernel that works + the one that returns)
-            std::unique_ptr<LaunchScope> auto_scope;
-            const double bytes1 = sizeof(T) * static_cast<double>(B) * (C * (static_cast<double>(H) * W + 2.0 * Hi * Wi) + 3.0 * H * W);
-            if (adaptive) {
-                auto_scope.reset(new LaunchScope("resample2d_bwd_input1_auto", st, bytes1));
-                const int segs_x = static_cast<int>((W + kWave - 1) / kWave);
-                const int64_t nseg = B * H * segs_x;
-                sel_limit = static_cast<int>(nseg / 4 > 0 ? nseg / 4 : 1);          // "smooth": fewer than a quarter of the row segments irregular
-                if (zero_fill(sel, sizeof(int), st)) return FFWM_ERR_LAUNCH;
-                const int per = kBlock / kWave;
-                int64_t pre_blocks = (nseg + per - 1) / per;
-                if (pre_blocks > 1024) pre_blocks = 1024;
-                hipLaunchKernelGGL(rs_flow_irregular_kernel, dim3(static_cast<unsigned>(pre_blocks)), dim3(kBlock), 0, st, in2, sel,
-                                   (int)H, (int)W, segs_x, nseg);
-                if (int rc = check_launch("ffwm_resample2d_backward(flow regularity)")) return rc;
-            }
-            const bool run_taplane = gin1 && half == 2 && (variant == 0 || variant == 5) && !tile_only;
-            const bool run_tile = gin1 && (adaptive || tile_only || (!run_taplane && (plane_lds > 131072 || variant == 2)));
-            if (run_taplane) {
-                // one pixel's 16 taps x 4 channels per LDS atomic instruction -- bank-conflict-free for any flow
-                // default: 4 waves x 2 rows = 64 x 8 pixel tiles, two blocks per CU (56 KB box + 22 KB staging each); variant 5: 8 waves x 2 rows
-                // (one block per CU, a quarter fewer fold atomics: measured 1.61 against 1.53 ms at [8,64,512,512])
-                const int nw = variant == 5 ? 8 : 4, rpt = 2;
-                const int th = nw * rpt;
-                const int tiles_y = static_cast<int>((H + th - 1) / th);
-                int cs, cslabs;
-                slabs(B * tiles_x * tiles_y, cs, cslabs);
-                const unsigned grid = static_cast<unsigned>(B * tiles_x * tiles_y * cslabs);
-                const int ncell = (th + 12) * 88;
-                const int ps = ncell + ((4 - ncell % 32) + 32) % 32;
-                const size_t lds = static_cast<size_t>(4) * ps * sizeof(double) + static_cast<size_t>(nw) * (16 + 4) * 65 * sizeof(float);
-                std::unique_ptr<LaunchScope> ls;
-                if (!adaptive) ls.reset(new LaunchScope("resample2d_bwd_input1_taplane", st, bytes1));
-                if (nw == 8) {
-                    allow_large_lds(reinterpret_cast<const void*>(rs_bwd1_taplane_kernel<2, 8>));
-                    hipLaunchKernelGGL((rs_bwd1_taplane_kernel<2, 8>), dim3(grid), dim3(8 * kWave), lds, st, in2, gout, gin1, (int)C, (int)Hi,
-                                       (int)Wi, (int)H, (int)W, quirk, tiles_x, tiles_y, cslabs, cs, remap, sel, sel_limit, 0);
-                } else {
-                    allow_large_lds(reinterpret_cast<const void*>(rs_bwd1_taplane_kernel<2, 4>));
-                    hipLaunchKernelGGL((rs_bwd1_taplane_kernel<2, 4>), dim3(grid), dim3(4 * kWave), lds, st, in2, gout, gin1, (int)C, (int)Hi,
-                                       (int)Wi, (int)H, (int)W, quirk, tiles_x, tiles_y, cslabs, cs, remap, sel, sel_limit, 0);
-                }
-                if (int rc = check_launch("ffwm_resample2d_backward(input1, tap-lane)")) return rc;
-            }
-            if (run_tile) {
-                const int rpt = H >= 32 ? (options().rs_bwd1_rpt == 2 ? 2 : 4) : 1;
-                const int tiles_y = static_cast<int>((H + 4 * rpt - 1) / (4 * rpt));
-                int cs, cslabs;
-                slabs(B * tiles_x * tiles_y, cs, cslabs);
-                const unsigned grid = static_cast<unsigned>(B * tiles_x * tiles_y * cslabs);
-                const bool fixed_cells = options().rs_bwd1_fixed != 2;          // 32-bit fixed-point box cells (round 5); 2 = double cells
-                const size_t lds = static_cast<size_t>(4 * rpt + 12) * kRsBoxW * 4 * (fixed_cells ? sizeof(int) : sizeof(double));
-                std::unique_ptr<LaunchScope> ls;
-                if (!adaptive) ls.reset(new LaunchScope("resample2d_bwd_input1_tile", st, bytes1));
-#define FFWM_RS_B1T_(HH, RR, FX)                                                                              \
-    do {                                                                                                      \
-        allow_large_lds(reinterpret_cast<const void*>(rs_bwd1_tile_kernel<HH, RR, FX>));                      \
-        hipLaunchKernelGGL((rs_bwd1_tile_kernel<HH, RR, FX>), dim3(grid), dim3(kBlock), lds, st, in2, gout, gin1, (int)C, \
-                           (int)Hi, (int)Wi, (int)H, (int)W, quirk, tiles_x, tiles_y, cslabs, cs, remap, \
-                           adaptive ? sel : nullptr, sel_limit, 1); \
-    } while (0)
-#define FFWM_RS_B1T(HH, RR) do { if (fixed_cells) FFWM_RS_B1T_(HH, RR, true); else FFWM_RS_B1T_(HH, RR, false); } while (0)
-                if (rpt == 4) { if (half == 1) FFWM_RS_B1T(1, 4); else if (half == 2) FFWM_RS_B1T(2, 4); else FFWM_RS_B1T(3, 4); }
-                else if (rpt == 2) { if (half == 1) FFWM_RS_B1T(1, 2); else if (half == 2) FFWM_RS_B1T(2, 2); else FFWM_RS_B1T(3, 2); }
-                else { if (half == 1) FFWM_RS_B1T(1, 1); else if (half == 2) FFWM_RS_B1T(2, 1); else FFWM_RS_B1T(3, 1); }
-#undef FFWM_RS_B1T
-#undef FFWM_RS_B1T_
-                if (int rc = check_launch("ffwm_resample2d_backward(input1, tile)")) return rc;
-            }
-            auto_scope.reset();
-            if (run_taplane || run_tile) gin1 = nullptr;
-            if (gin2) {
-                const int tiles_y = static_cast<int>((H + 3) / 4);
-                int cs, cslabs;
-                slabs(B * tiles_x * tiles_y, cs, cslabs);
-                const unsigned grid = static_cast<unsigned>(B * tiles_x * tiles_y * cslabs);
-                const size_t lds = static_cast<size_t>(2) * 16 * kRsBoxW * 16;
-                if (cslabs > 1)          // the slabs' partial results are added atomically
-                    if (zero_fill(gin2, sizeof(T) * static_cast<size_t>(B) * 3 * H * W, st)) return FFWM_ERR_LAUNCH;
-                const double bytes = sizeof(T) * static_cast<double>(B) * H * W * (2.0 * C + 6.0);
-                LaunchScope ls("resample2d_bwd_input2_lds", st, bytes);
-#define FFWM_RS_B2L(HH)                                                                                       \
-    hipLaunchKernelGGL((rs_bwd2_lds_kernel<HH, 1>), dim3(grid), dim3(kBlock), lds, st, in1, in2, gout, gin2, (int)C, \
-                       (int)Hi, (int)Wi, (int)H, (int)W, tiles_x, tiles_y, cslabs, cs, remap)
-                if (half == 1) FFWM_RS_B2L(1); else if (half == 2) FFWM_RS_B2L(2); else FFWM_RS_B2L(3);
-#undef FFWM_RS_B2L
-                if (int rc = check_launch("ffwm_resample2d_backward(input2, lds)")) return rc;
-                gin2 = nullptr;
-            }
-            if (!gin1 && !gin2) return FFWM_OK;
+        // one profiling scope over the whole sequence of an adaptive call (pre-pass + the kernel that works + the one that returns)
+        std::unique_ptr<LaunchScope> auto_scope;
+        int sel_limit = 0;
+        if (r.adaptive) {
+            auto_scope.reset(new LaunchScope("resample2d_bwd_input1_auto", st, bytes1));
+            const int segs_x = static_cast<int>((W + kWave - 1) / kWave);
+            const int64_t nseg = B * H * segs_x;
+            sel_limit = static_cast<int>(nseg / 4 > 0 ? nseg / 4 : 1);          // "smooth": fewer than a quarter of the row segments irregular
+            if (zero_fill(r.sel, sizeof(int), st)) return FFWM_ERR_LAUNCH;
+            const int per = kBlock / kWave;
+            hipLaunchKernelGGL(rs_flow_irregular_kernel, dim3(capped_grid((nseg + per - 1) / per, 1024)), dim3(kBlock), 0, st, in2, r.sel,
+                               (int)H, (int)W, segs_x, nseg);
+            if (int rc = check_launch("ffwm_resample2d_backward(flow regularity)")) return rc;
+        }
+        if (r.taplane) {
+            // one pixel's 16 taps x 4 channels per LDS atomic instruction -- bank-conflict-free for any flow
+            std::unique_ptr<LaunchScope> ls;
+            if (!r.adaptive) ls.reset(new LaunchScope("resample2d_bwd_input1_taplane", st, bytes1));
+            ok &= dispatch<8, 4>(r.taplane_waves, [&](auto NW) {
+                constexpr int RPT = 2, TH = NW.value * RPT;
+                const RsTiles t = plan_tiles(B, C, H, W, kTileX, TH);
+                constexpr int NCELL = (TH + 12) * 88, PS = NCELL + ((4 - NCELL % 32) + 32) % 32;
+                const size_t lds = static_cast<size_t>(4) * PS * sizeof(double) + static_cast<size_t>(NW.value) * (16 + 4) * 65 * sizeof(float);
+                auto kfn = rs_bwd1_taplane_kernel<2, NW.value>;
+                allow_large_lds(reinterpret_cast<const void*>(kfn));
+                hipLaunchKernelGGL(kfn, dim3(t.grid), dim3(NW.value * kWave), lds, st, in2, gout, gin1, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, quirk,
+                                   t.tiles_x, t.tiles_y, t.cslabs, t.cs, remap, r.sel, sel_limit, 0);
+            });
+            if (int rc = ok ? check_launch("ffwm_resample2d_backward(input1, tap-lane)") : no_kernel("ffwm_resample2d_backward(input1, tap-lane)")) return rc;
+        }
+        if (r.tile) {
+            std::unique_ptr<LaunchScope> ls;
+            if (!r.adaptive) ls.reset(new LaunchScope("resample2d_bwd_input1_tile", st, bytes1));
+            ok &= dispatch<1, 2, 3>(half, [&](auto HALF) {
+                return dispatch<4, 2, 1>(r.tile_rpt, [&](auto RPT) {
+                    dispatch<true, false>(r.tile_fixed, [&](auto FIXED) {
+                        constexpr int TH = 4 * RPT.value;
+                        const RsTiles t = plan_tiles(B, C, H, W, kTileX, TH);
+                        const size_t lds = static_cast<size_t>(TH + 12) * kRsBoxW * 4 * (FIXED.value ? sizeof(int) : sizeof(double));
+                        auto kfn = rs_bwd1_tile_kernel<HALF.value, RPT.value, FIXED.value>;
+                        allow_large_lds(reinterpret_cast<const void*>(kfn));
+                        hipLaunchKernelGGL(kfn, dim3(t.grid), dim3(kBlock), lds, st, in2, gout, gin1, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, quirk,
+                                           t.tiles_x, t.tiles_y, t.cslabs, t.cs, remap, r.sel, sel_limit, 1);
+                    });
+                });
+            });
+            if (int rc = ok ? check_launch("ffwm_resample2d_backward(input1, tile)") : no_kernel("ffwm_resample2d_backward(input1, tile)")) return rc;
+        }
+        auto_scope.reset();
+        if (r.in2_lds) {
+            constexpr int RPT = 1, TH = 4 * RPT;          // rs_bwd2_lds_kernel<HALF, RPT>: two staging buffers of TH + 12 rows
+            const RsTiles t = plan_tiles(B, C, H, W, kTileX, TH);
+            const size_t lds = static_cast<size_t>(2) * (TH + 12) * kRsBoxW * 16;
+            if (t.cslabs > 1)          // the slabs' partial results are added atomically
+                if (zero_fill(gin2, sizeof(T) * static_cast<size_t>(B) * 3 * H * W, st)) return FFWM_ERR_LAUNCH;
+            LaunchScope ls("resample2d_bwd_input2_lds", st, bytes2);
+            ok &= dispatch<1, 2, 3>(half, [&](auto HALF) {
+                hipLaunchKernelGGL((rs_bwd2_lds_kernel<HALF.value, RPT>), dim3(t.grid), dim3(kBlock), lds, st, in1, in2, gout, gin2, (int)C, (int)Hi,
+                                   (int)Wi, (int)H, (int)W, t.tiles_x, t.tiles_y, t.cslabs, t.cs, remap);
+            });
+            if (int rc = ok ? check_launch("ffwm_resample2d_backward(input2, lds)") : no_kernel("ffwm_resample2d_backward(input2, lds)")) return rc;
         }
     }
-    if (gin1 && plane_lds <= 131072 && half >= 1 && half <= 3 && options().scatter_variant != 1) {      // fp64, dilation > 1, or scatter_variant 2
-        const double bytes = sizeof(T) * static_cast<double>(B) * (C * (static_cast<double>(H) * W + 2.0 * Hi * Wi) + 3.0 * H * W);
+    if (r.plane) {
+        const size_t plane_lds = static_cast<size_t>(Hi) * Wi * sizeof(double);
         int cg = static_cast<int>(131072 / plane_lds);
         if (cg > C) cg = static_cast<int>(C);
-        while (cg > 1 && B * ((C + cg - 1) / cg) < 512) cg = (cg + 1) / 2;   // keep >= 2 blocks per CU
+        cg = halve_slab(cg, C, B, 512, 1);   // keep >= 2 blocks per CU
         const int groups = static_cast<int>((C + cg - 1) / cg);
         int nsplit = 1;                      // the per-pixel Gaussian weights (double exp) dominate: fill the chip
         while (B * groups * nsplit < 256 && nsplit * 2 * kPlaneThreads <= H * W) nsplit *= 2;
         const unsigned grid = static_cast<unsigned>(B * groups * nsplit);
-        const size_t lds = static_cast<size_t>(cg) * plane_lds;
-        allow_large_lds(reinterpret_cast<const void*>(rs_bwd1_plane_kernel<T, 1>));
-        allow_large_lds(reinterpret_cast<const void*>(rs_bwd1_plane_kernel<T, 2>));
-        allow_large_lds(reinterpret_cast<const void*>(rs_bwd1_plane_kernel<T, 3>));
         {
-            LaunchScope ls("resample2d_bwd_input1_plane", st, bytes);
-            if (half == 1)
-                hipLaunchKernelGGL((rs_bwd1_plane_kernel<T, 1>), dim3(grid), dim3(kPlaneThreads), lds, st, in2, gout, gin1,
+            LaunchScope ls("resample2d_bwd_input1_plane", st, bytes1);
+            ok &= dispatch<1, 2, 3>(half, [&](auto HALF) {
+                auto kfn = rs_bwd1_plane_kernel<T, HALF.value>;
+                allow_large_lds(reinterpret_cast<const void*>(kfn));
+                hipLaunchKernelGGL(kfn, dim3(grid), dim3(kPlaneThreads), static_cast<size_t>(cg) * plane_lds, st, in2, gout, gin1,
                                    (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, quirk, cg, groups, nsplit);
-            else if (half == 2)
-                hipLaunchKernelGGL((rs_bwd1_plane_kernel<T, 2>), dim3(grid), dim3(kPlaneThreads), lds, st, in2, gout, gin1,
-                                   (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, quirk, cg, groups, nsplit);
-            else
-                hipLaunchKernelGGL((rs_bwd1_plane_kernel<T, 3>), dim3(grid), dim3(kPlaneThreads), lds, st, in2, gout, gin1,
-                                   (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, quirk, cg, groups, nsplit);
+            });
         }
-        if (int rc = check_launch("ffwm_resample2d_backward(input1, plane)")) return rc;
-        gin1 = nullptr;
+        if (int rc = ok ? check_launch("ffwm_resample2d_backward(input1, plane)") : no_kernel("ffwm_resample2d_backward(input1, plane)")) return rc;
     }
-    if (gin1) {
-        const double bytes = sizeof(T) * static_cast<double>(B) * H * W * (2.0 * C + 3.0);
+    if (r.pixels1) {
         const Geometry g = plan(B, C, H, W, 32);
-        LaunchScope ls("resample2d_bwd_input1", st, bytes);
-#define FFWM_RS_B1(HH)                                                                               \
-    case 2 * HH:                                                                                     \
-        hipLaunchKernelGGL((rs_bwd1_kernel<T, HH>), dim3(g.grid), dim3(kBlock), 0, st, in2, gout,     \
-                           gin1, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, quirk, g.tiles_x,     \
-                           g.tiles_y, g.cslabs, g.cs, remap);                                        \
-        break;
-        switch (ks & ~1) {
-            FFWM_RS_B1(1) FFWM_RS_B1(2) FFWM_RS_B1(3)
-            default: {
-                const int64_t n = B * C * H * W;
-                hipLaunchKernelGGL((rs_bwd1_generic<T>), dim3(generic_grid(n)), dim3(kBlock), 0, st, in2,
-                                   gout, gin1, n, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, ks, dil, quirk);
-            }
+        LaunchScope ls("resample2d_bwd_input1", st, sizeof(T) * static_cast<double>(B) * H * W * (2.0 * C + 3.0));
+        const bool fast = dispatch<1, 2, 3>(half, [&](auto HALF) {
+            hipLaunchKernelGGL((rs_bwd1_kernel<T, HALF.value>), dim3(g.grid), dim3(kBlock), 0, st, in2, gout, gin1, (int)C, (int)Hi, (int)Wi,
+                               (int)H, (int)W, dil, quirk, g.tiles_x, g.tiles_y, g.cslabs, g.cs, remap);
+        });
+        if (!fast) {
+            const int64_t n = B * C * H * W;
+            hipLaunchKernelGGL((rs_bwd1_generic<T>), dim3(generic_grid(n)), dim3(kBlock), 0, st, in2,
+                               gout, gin1, n, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, ks, dil, quirk);
         }
-#undef FFWM_RS_B1
         if (int rc = check_launch("ffwm_resample2d_backward(input1)")) return rc;
     }
-    if (gin2) {
-        const double bytes = sizeof(T) * static_cast<double>(B) * H * W * (2.0 * C + 6.0);
+    if (r.in2_pixels) {
         const int tiles_x = static_cast<int>((W + kWave - 1) / kWave);
         const unsigned grid = static_cast<unsigned>(B * H * tiles_x);
-        LaunchScope ls("resample2d_bwd_input2", st, bytes);
-#define FFWM_RS_B2(HH)                                                                               \
-    case 2 * HH:                                                                                     \
-        hipLaunchKernelGGL((rs_bwd2_kernel<T, HH>), dim3(grid), dim3(kBlock), 0, st, in1, in2, gout,  \
-                           gin2, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, tiles_x);            \
-        break;
-        switch (ks & ~1) {
-            FFWM_RS_B2(1) FFWM_RS_B2(2) FFWM_RS_B2(3)
-            default: {
-                const int64_t n = B * 3 * H * W;
-                hipLaunchKernelGGL((rs_bwd2_generic<T>), dim3(generic_grid(n)), dim3(kBlock), 0, st, in1,
-                                   in2, gout, gin2, n, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, ks, dil);
-            }
+        LaunchScope ls("resample2d_bwd_input2", st, bytes2);
+        const bool fast = dispatch<1, 2, 3>(half, [&](auto HALF) {
+            hipLaunchKernelGGL((rs_bwd2_kernel<T, HALF.value>), dim3(grid), dim3(kBlock), 0, st, in1, in2, gout, gin2, (int)C, (int)Hi, (int)Wi,
+                               (int)H, (int)W, dil, tiles_x);
+        });
+        if (!fast) {
+            const int64_t n = B * 3 * H * W;
+            hipLaunchKernelGGL((rs_bwd2_generic<T>), dim3(generic_grid(n)), dim3(kBlock), 0, st, in1,
+                               in2, gout, gin2, n, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, ks, dil);
         }
-#undef FFWM_RS_B2
         if (int rc = check_launch("ffwm_resample2d_backward(input2)")) return rc;
     }
     return FFWM_OK;
@@ -2357,12 +2296,11 @@ extern "C" int ffwm_resample2d_forward(const void* input1, const void* input2, v
     const char* fn = "ffwm_resample2d_forward";
     FFWM_REQUIRE(input1 && input2 && output, FFWM_ERR_ARG, "%s: NULL tensor pointer", fn);
     if (int rc = check_dims(fn, B, C, Hi, Wi, H, W, kernel_size, dilation, dtype)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == FFWM_F32)
-        return launch_fwd<float>((const float*)input1, (const float*)input2, (float*)output, B, C, Hi, Wi,
-                                 H, W, kernel_size, dilation, st);
-    return launch_fwd<double>((const double*)input1, (const double*)input2, (double*)output, B, C, Hi, Wi,
-                              H, W, kernel_size, dilation, st);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_fwd<T>((const T*)input1, (const T*)input2, (T*)output, B, C, Hi, Wi, H, W, kernel_size, dilation,
+                             static_cast<hipStream_t>(stream));
+    });
 }
 
 extern "C" int ffwm_resample2d_backward(const void* input1, const void* input2, const void* grad_output,
@@ -2373,15 +2311,12 @@ extern "C" int ffwm_resample2d_backward(const void* input1, const void* input2, 
     FFWM_REQUIRE(input1 && input2 && grad_output, FFWM_ERR_ARG, "%s: NULL tensor pointer", fn);
     if (int rc = check_dims(fn, B, C, Hi, Wi, H, W, kernel_size, dilation, dtype)) return rc;
     if (!grad_input1 && !grad_input2) return FFWM_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
     FFWM_REQUIRE(reference_quirk >= 0 && reference_quirk <= 3, FFWM_ERR_ARG, "%s: reference_quirk is a 2-bit flag word", fn);
-    if (dtype == FFWM_F32)
-        return launch_bwd<float>((const float*)input1, (const float*)input2, (const float*)grad_output,
-                                 (float*)grad_input1, (float*)grad_input2, B, C, Hi, Wi, H, W, kernel_size,
-                                 dilation, reference_quirk, st);
-    return launch_bwd<double>((const double*)input1, (const double*)input2, (const double*)grad_output,
-                              (double*)grad_input1, (double*)grad_input2, B, C, Hi, Wi, H, W, kernel_size,
-                              dilation, reference_quirk, st);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_bwd<T>((const T*)input1, (const T*)input2, (const T*)grad_output, (T*)grad_input1, (T*)grad_input2, B, C, Hi, Wi, H, W,
+                             kernel_size, dilation, reference_quirk, static_cast<hipStream_t>(stream));
+    });
 }
 
 // grad_output read through its element strides (NULL / contiguous: the entry point above).  Any other layout takes the per-element
@@ -2404,30 +2339,24 @@ extern "C" int ffwm_resample2d_backward_strided(const void* input1, const void* 
     if (!grad_input1 && !grad_input2) return FFWM_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const GoStrides gs{grad_output_strides[0], grad_output_strides[1], grad_output_strides[2], grad_output_strides[3]};
-    const size_t esz = dtype == FFWM_F32 ? 4 : 8;
-    if (grad_input1 && (reference_quirk & 2))
-        if (zero_fill(grad_input1, esz * static_cast<size_t>(B) * C * Hi * Wi, st)) return FFWM_ERR_LAUNCH;
-    LaunchScope ls("resample2d_bwd_strided", st, static_cast<double>(esz) * B * (C * (static_cast<double>(H) * W + 2.0 * Hi * Wi) + 6.0 * H * W));
     const int ks = kernel_size & ~1, quirk = reference_quirk & 1;
-    if (grad_input1) {
-        const int64_t n = B * C * H * W;
-        if (dtype == FFWM_F32)
-            hipLaunchKernelGGL((rs_bwd1_generic<float>), dim3(generic_grid(n)), dim3(kBlock), 0, st, (const float*)input2, (const float*)grad_output,
-                               (float*)grad_input1, n, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, ks, dilation, quirk, gs);
-        else
-            hipLaunchKernelGGL((rs_bwd1_generic<double>), dim3(generic_grid(n)), dim3(kBlock), 0, st, (const double*)input2, (const double*)grad_output,
-                               (double*)grad_input1, n, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, ks, dilation, quirk, gs);
-        if (int rc = check_launch(fn)) return rc;
-    }
-    if (grad_input2) {
-        const int64_t n = B * 3 * H * W;
-        if (dtype == FFWM_F32)
-            hipLaunchKernelGGL((rs_bwd2_generic<float>), dim3(generic_grid(n)), dim3(kBlock), 0, st, (const float*)input1, (const float*)input2,
-                               (const float*)grad_output, (float*)grad_input2, n, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, ks, dilation, gs);
-        else
-            hipLaunchKernelGGL((rs_bwd2_generic<double>), dim3(generic_grid(n)), dim3(kBlock), 0, st, (const double*)input1, (const double*)input2,
-                               (const double*)grad_output, (double*)grad_input2, n, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, ks, dilation, gs);
-        if (int rc = check_launch(fn)) return rc;
-    }
-    return FFWM_OK;
+    return by_dtype(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        if (grad_input1 && (reference_quirk & 2))
+            if (zero_fill(grad_input1, sizeof(T) * static_cast<size_t>(B) * C * Hi * Wi, st)) return FFWM_ERR_LAUNCH;
+        LaunchScope ls("resample2d_bwd_strided", st, static_cast<double>(sizeof(T)) * B * (C * (static_cast<double>(H) * W + 2.0 * Hi * Wi) + 6.0 * H * W));
+        if (grad_input1) {
+            const int64_t n = B * C * H * W;
+            hipLaunchKernelGGL((rs_bwd1_generic<T>), dim3(generic_grid(n)), dim3(kBlock), 0, st, (const T*)input2, (const T*)grad_output,
+                               (T*)grad_input1, n, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, ks, dilation, quirk, gs);
+            if (int rc = check_launch(fn)) return rc;
+        }
+        if (grad_input2) {
+            const int64_t n = B * 3 * H * W;
+            hipLaunchKernelGGL((rs_bwd2_generic<T>), dim3(generic_grid(n)), dim3(kBlock), 0, st, (const T*)input1, (const T*)input2,
+                               (const T*)grad_output, (T*)grad_input2, n, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, ks, dilation, gs);
+            if (int rc = check_launch(fn)) return rc;
+        }
+        return FFWM_OK;
+    });
 }

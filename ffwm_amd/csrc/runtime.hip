@@ -126,8 +126,7 @@ Geometry plan(int64_t B, int64_t C, int64_t H, int64_t W, int cs_default) {
     const int64_t spatial = B * g.tiles_x * g.tiles_y;
     int cs = options().channel_slab > 0 ? options().channel_slab : cs_default;
     if (cs > C) cs = static_cast<int>(C);
-    while (cs > 1 && spatial * ((C + cs - 1) / cs) < 4096) cs = (cs + 1) / 2;   // >= 16 blocks per CU
-    g.cs = cs;
+    g.cs = cs = halve_slab(cs, C, spatial, 4096, 1);   // >= 16 blocks per CU
     g.cslabs = static_cast<int>((C + cs - 1) / cs);
     g.grid = static_cast<unsigned>(spatial * g.cslabs);
     return g;
@@ -284,47 +283,14 @@ int ffwm_zero_fill(void* p, int64_t bytes, void* stream) {
 int ffwm_set_option(const char* key, int value) {
     if (!key) return FFWM_ERR_ARG;
     Options& o = options();
+    static const struct { const char* key; int Options::*field; } table[] = {
+#define FFWM_OPTION_KEY(name, def) {#name, &Options::name},
+        FFWM_OPTIONS(FFWM_OPTION_KEY)
+#undef FFWM_OPTION_KEY
+    };
     int* slot = nullptr;
-    if (!strcmp(key, "be_fwd_variant")) slot = &o.be_fwd_variant;
-    else if (!strcmp(key, "be_bwd_variant")) slot = &o.be_bwd_variant;
-    else if (!strcmp(key, "channel_slab")) slot = &o.channel_slab;
-    else if (!strcmp(key, "xcd_remap")) slot = &o.xcd_remap;
-    else if (!strcmp(key, "warp_multi_order")) slot = &o.warp_multi_order;
-    else if (!strcmp(key, "rows_per_thread")) slot = &o.rows_per_thread;
-    else if (!strcmp(key, "scatter_variant")) slot = &o.scatter_variant;
-    else if (!strcmp(key, "be_bwd_halo")) slot = &o.be_bwd_halo;
-    else if (!strcmp(key, "warp_fwd_variant")) slot = &o.warp_fwd_variant;
-    else if (!strcmp(key, "warp_nt")) slot = &o.warp_nt;
-    else if (!strcmp(key, "warp_pair_loads")) slot = &o.warp_pair_loads;
-    else if (!strcmp(key, "warp_multi_lds")) slot = &o.warp_multi_lds;
-    else if (!strcmp(key, "warp_multi_planes")) slot = &o.warp_multi_planes;
-    else if (!strcmp(key, "conv_wgrad_wino")) slot = &o.conv_wgrad_wino;
-    else if (!strcmp(key, "be_bwd_rows")) slot = &o.be_bwd_rows;
-    else if (!strcmp(key, "rs_fwd_variant")) slot = &o.rs_fwd_variant;
-    else if (!strcmp(key, "rs_bwd1_variant")) slot = &o.rs_bwd1_variant;
-    else if (!strcmp(key, "conv_tile_variant")) slot = &o.conv_tile_variant;
-    else if (!strcmp(key, "conv_thin_tail")) slot = &o.conv_thin_tail;
-    else if (!strcmp(key, "conv_wino_raw")) slot = &o.conv_wino_raw;
-    else if (!strcmp(key, "conv_wino_ws")) slot = &o.conv_wino_ws;
-    else if (!strcmp(key, "conv_wgrad_slice_target")) slot = &o.conv_wgrad_slice_target;
-    else if (!strcmp(key, "conv_fwd_split_target")) slot = &o.conv_fwd_split_target;
-    else if (!strcmp(key, "conv_wino_split")) slot = &o.conv_wino_split;
-    else if (!strcmp(key, "conv_wgrad_unsliced")) slot = &o.conv_wgrad_unsliced;
-    else if (!strcmp(key, "zero_fill_memset")) slot = &o.zero_fill_memset;
-    else if (!strcmp(key, "be_bwd_fixed")) slot = &o.be_bwd_fixed;
-    else if (!strcmp(key, "be_bwd_flush")) slot = &o.be_bwd_flush;
-    else if (!strcmp(key, "ba_bwd_fused")) slot = &o.ba_bwd_fused;
-    else if (!strcmp(key, "ba_bwd_pix")) slot = &o.ba_bwd_pix;
-    else if (!strcmp(key, "ba_fwd_pix")) slot = &o.ba_fwd_pix;
-    else if (!strcmp(key, "conv_thin_variant")) slot = &o.conv_thin_variant;
-    else if (!strcmp(key, "rs_bwd1_owned")) slot = &o.rs_bwd1_owned;
-    else if (!strcmp(key, "warp_feat_fixed")) slot = &o.warp_feat_fixed;
-    else if (!strcmp(key, "rs_bwd1_owned_blocks")) slot = &o.rs_bwd1_owned_blocks;
-    else if (!strcmp(key, "rs_bwd1_owned_min_pixels")) slot = &o.rs_bwd1_owned_min_pixels;
-    else if (!strcmp(key, "rs_bwd1_fixed")) slot = &o.rs_bwd1_fixed;
-    else if (!strcmp(key, "rs_bwd1_rpt")) slot = &o.rs_bwd1_rpt;
-    else if (!strcmp(key, "warp_feat_gps")) slot = &o.warp_feat_gps;
-    else if (!strcmp(key, "conv_fwd_kfast")) slot = &o.conv_fwd_kfast;
+    for (const auto& t : table)
+        if (!strcmp(key, t.key)) slot = &(o.*t.field);
     if (!slot) {
         set_error("ffwm_set_option: unknown key '%s'", key);
         return FFWM_ERR_ARG;

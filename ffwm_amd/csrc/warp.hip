@@ -1507,198 +1507,205 @@ int check_dims(const char* fn, int64_t B, int64_t C, int64_t Hi, int64_t Wi, int
     return FFWM_OK;
 }
 
+// warp_fwd_variant: 0 = auto (LDS-staged tiles for large float outputs), 1 = direct gathers, 2 = LDS-staged.  The same rule sends
+// the forward, a problem of a multi forward launch and the d(flow)-alone backward to the LDS-tile kernels.
+// (measured: the tile kernel wins once the output no longer sits in L2 -- 4.6 vs 3.4 TB/s on [32,64,256,256];
+//  on the <= 34 MB tensors of netG the direct kernel is as fast or faster)
+inline bool fwd_wants_lds(int64_t B, int64_t C, int64_t H, int64_t W, size_t esz) {
+    const int variant = options().warp_fwd_variant;
+    return esz == 4 && (variant == 2 || (variant == 0 && H >= 64 && W >= 64 && B * C * H * W >= (1LL << 24)));
+}
+
+// Launch geometry of the LDS-tile kernels (kWlTileX x kWlTileY pixels): the channel slab starts at channel_slab or `cs_default` and is
+// halved down to `cs_floor` until the launch has `min_blocks` blocks.
+struct LdsTiles {
+    int txs, tys, cs, cslabs;
+    unsigned grid;
+};
+inline LdsTiles plan_lds_tiles(int64_t B, int64_t C, int64_t H, int64_t W, int cs_default, int cs_floor, int min_blocks) {
+    LdsTiles t;
+    t.txs = static_cast<int>((W + kWlTileX - 1) / kWlTileX);
+    t.tys = static_cast<int>((H + kWlTileY - 1) / kWlTileY);
+    int cs = options().channel_slab > 0 ? options().channel_slab : cs_default;
+    if (cs > C) cs = static_cast<int>(C);
+    t.cs = halve_slab(cs, C, B * t.txs * t.tys, min_blocks, cs_floor);
+    t.cslabs = static_cast<int>((C + t.cs - 1) / t.cs);
+    t.grid = static_cast<unsigned>(B * t.txs * t.tys * t.cslabs);
+    return t;
+}
+
 template <typename T>
 int launch_fwd(const T* feat, const T* flow, T* out, int64_t B, int64_t C, int64_t Hi, int64_t Wi,
                int64_t H, int64_t W, int flip, hipStream_t st) {
     const double bytes = sizeof(T) * static_cast<double>(B) *
                          (static_cast<double>(C) * Hi * Wi + 2.0 * H * W + (flip ? 2.0 : 1.0) * C * H * W);
-    const Geometry g = plan(B, C, H, W, 16);
     const int remap = options().xcd_remap;
     LaunchScope ls(scope_at(flip ? "warp_flipcat_fwd" : "warp_fwd", H), st, bytes);
-    // warp_fwd_variant: 0 = auto (LDS-staged tiles for large float outputs), 1 = direct gathers, 2 = LDS-staged
     if constexpr (sizeof(T) == 4) {
-        const int variant = options().warp_fwd_variant;
-        // (measured: the tile kernel wins once the output no longer sits in L2 -- 4.6 vs 3.4 TB/s on [32,64,256,256];
-        //  on the <= 34 MB tensors of netG the direct kernel is as fast or faster)
-        if (variant == 2 || (variant == 0 && H >= 64 && W >= 64 && B * C * H * W >= (1LL << 24))) {
-            const int txs = static_cast<int>((W + kWlTileX - 1) / kWlTileX), tys = static_cast<int>((H + kWlTileY - 1) / kWlTileY);
-            int cs = options().channel_slab > 0 ? options().channel_slab : 32;      // measured at [32,64,256,256]: 8 / 16 / 32 / 64 -> 4.4 / 4.8 / 5.0 / 4.9 TB/s
-            if (cs > C) cs = static_cast<int>(C);
-            while (cs > 2 && B * txs * tys * ((C + cs - 1) / cs) < 2048) cs = (cs + 1) / 2;
-            const int cslabs = static_cast<int>((C + cs - 1) / cs);
-            const unsigned grid = static_cast<unsigned>(B * txs * tys * cslabs);
+        if (fwd_wants_lds(B, C, H, W, sizeof(T))) {
+            const LdsTiles t = plan_lds_tiles(B, C, H, W, 32, 2, 2048);      // measured at [32,64,256,256]: 8 / 16 / 32 / 64 -> 4.4 / 4.8 / 5.0 / 4.9 TB/s
             const int nt = sizeof(T) * static_cast<double>(B) * C * H * W * (flip ? 2 : 1) >= 64.0 * 1024 * 1024 ? 1 : 0;   // streaming stores
-            if (flip)
-                hipLaunchKernelGGL((warp_fwd_lds_kernel<true>), dim3(grid), dim3(kBlock), 0, st, (const float*)feat,
-                                   (const float*)flow, (float*)out, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, txs, tys, cslabs,
-                                   cs, remap, nt);
-            else
-                hipLaunchKernelGGL((warp_fwd_lds_kernel<false>), dim3(grid), dim3(kBlock), 0, st, (const float*)feat,
-                                   (const float*)flow, (float*)out, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, txs, tys, cslabs,
-                                   cs, remap, nt);
+            dispatch<true, false>(flip != 0, [&](auto FL) {
+                hipLaunchKernelGGL((warp_fwd_lds_kernel<FL.value>), dim3(t.grid), dim3(kBlock), 0, st, (const float*)feat, (const float*)flow,
+                                   (float*)out, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, t.txs, t.tys, t.cslabs, t.cs, remap, nt);
+            });
             return check_launch("ffwm_warp_forward(lds)");
         }
     }
-    if (flip)
-        hipLaunchKernelGGL((warp_fwd_kernel<T, true>), dim3(g.grid), dim3(kBlock), 0, st, feat, flow, out,
+    const Geometry g = plan(B, C, H, W, 16);
+    dispatch<true, false>(flip != 0, [&](auto FL) {
+        hipLaunchKernelGGL((warp_fwd_kernel<T, FL.value>), dim3(g.grid), dim3(kBlock), 0, st, feat, flow, out,
                            (int)C, (int)Hi, (int)Wi, (int)H, (int)W, g.tiles_x, g.tiles_y, g.cslabs, g.cs, remap);
-    else
-        hipLaunchKernelGGL((warp_fwd_kernel<T, false>), dim3(g.grid), dim3(kBlock), 0, st, feat, flow, out,
-                           (int)C, (int)Hi, (int)Wi, (int)H, (int)W, g.tiles_x, g.tiles_y, g.cslabs, g.cs, remap);
+    });
     return check_launch("ffwm_warp_forward");
+}
+
+// warp_feat_fixed -> the owned-tile d(feat) kernel: 0 = double cells, two channels per group (rounds 3-5, the default); 1 = 32-bit
+// fixed-point cells on that kernel (round 6 experiment, OFF: correct, but hipcc cannot hold the kernel in 128 registers -- 64-104 bytes
+// of scratch reloaded inside the add loop, each behind an s_waitcnt vmcnt(0): 495 -> 900 us); 3 / 4 = fixed-point cells with a compact
+// per-pixel state (3 registers instead of 10), four / two channels per group: 551-588 / 498-528 us against the double cells' 474-535
+// on the same boxes -- the kernel is not bound by its LDS atomics (profiles/r06_warp_feat_fixed_negative.txt), so all of them stay
+// options.  COMPACT picks warp_bwd_feat_tile2_kernel<FL, CG, OV>, else warp_bwd_feat_tile_kernel<FL, CG, OV, FIXED>.
+template <bool COMPACT_, int CG_, bool FIXED_>
+struct WarpFeatTile {
+    static constexpr bool COMPACT = COMPACT_, FIXED = FIXED_;
+    static constexpr int CG = CG_;      // channels per group: the host counts the groups with it
+};
+template <class F>
+void select_warp_feat_tile(int warp_feat_fixed, F&& f) {
+    switch (warp_feat_fixed) {
+        case 1: return f(WarpFeatTile<false, 2, true>{});
+        case 3: return f(WarpFeatTile<true, 4, false>{});
+        case 4: return f(WarpFeatTile<true, 2, false>{});
+        default: return f(WarpFeatTile<false, 2, false>{});
+    }
+}
+
+// Which kernels a backward call gets (decided once, from the shape and the options; launch_bwd only launches).
+struct BwdRoute {
+    // d(feat), at most one of:
+    bool feat_planes;      // LDS-resident planes, no contended global atomics
+    bool feat_tiles;       // fp32, planes beyond LDS, resolution kept: owned tiles + the far complement
+    bool feat_pixels;      // the pixel-major kernel with global atomics (together with d(flow) when that is wanted too)
+    // d(flow), at most one of:
+    bool flow_lds;         // d(flow) alone on LDS-staged tiles (warp_bwd_flow_lds_body) for the same tensors the forward takes there; warp_multi_lds = 1: never
+    bool flow_pixels;      // the pixel-major kernel
+    bool overwrite;        // the owned tiles STORE grad_feat (flipcat bit 1: it arrives uninitialised)
+    bool clear_feat;       // ... every other path adds: the library clears it first
+    PlanePlan pp;
+};
+inline BwdRoute route_bwd(bool want_feat, bool want_flow, bool uninitialised, int64_t B, int64_t C, int64_t Hi, int64_t Wi, int64_t H,
+                          int64_t W, size_t esz) {
+    const bool atomics_only = options().scatter_variant == 1;
+    BwdRoute r;
+    r.pp = plan_planes(B, C, Hi * Wi, H * W, esz == 8 ? 2 : 8);
+    r.feat_planes = want_feat && r.pp.ok && !atomics_only;
+    r.feat_tiles = want_feat && !r.feat_planes && esz == 4 && Hi == H && Wi == W && !atomics_only;
+    r.feat_pixels = want_feat && !r.feat_planes && !r.feat_tiles;
+    r.flow_lds = want_flow && !r.feat_pixels && options().warp_multi_lds != 1 && fwd_wants_lds(B, C, H, W, esz);
+    r.flow_pixels = want_flow && !r.flow_lds;
+    r.overwrite = uninitialised && r.feat_tiles;
+    r.clear_feat = uninitialised && want_feat && !r.feat_tiles;
+    return r;
 }
 
 template <typename T>
 int launch_bwd(const T* feat, const T* flow, const T* gout, T* gfeat, T* gflow, int64_t B, int64_t C,
                int64_t Hi, int64_t Wi, int64_t H, int64_t W, int flipcat, hipStream_t st) {
-    const int flip = flipcat & 1;
+    const bool flip = (flipcat & 1) != 0;
     // flipcat bit 1: grad_feat is UNINITIALISED and must be produced whole (no caller zero-fill).  Only the owned-tile path stores
     // instead of adding; every other path gets the zero-fill it relies on from here.
-    bool ovw = (flipcat & 2) != 0 && gfeat != nullptr;
-    const double bytes = sizeof(T) * static_cast<double>(B) *
-                         (2.0 * C * Hi * Wi + 4.0 * H * W + (flip ? 2.0 : 1.0) * C * H * W);
+    const BwdRoute r = route_bwd(gfeat != nullptr, gflow != nullptr, (flipcat & 2) != 0, B, C, Hi, Wi, H, W, sizeof(T));
     const int remap = options().xcd_remap;
-    const PlanePlan pp = plan_planes(B, C, Hi * Wi, H * W, sizeof(T) == 8 ? 2 : 8);
-    const bool tile_path = sizeof(T) == 4 && gfeat && !(pp.ok && options().scatter_variant != 1) && Hi == H && Wi == W &&
-                           options().scatter_variant != 1;
-    if (ovw && !tile_path) {
+    const double esz = sizeof(T), out_elems = (flip ? 2.0 : 1.0) * C * H * W;     // (per batch item)
+    const double bytes_flow = esz * B * (static_cast<double>(C) * Hi * Wi + 4.0 * H * W + out_elems);
+    if (r.clear_feat)
         if (zero_fill(gfeat, sizeof(T) * static_cast<size_t>(B) * C * Hi * Wi, st)) return FFWM_ERR_LAUNCH;
-        ovw = false;
-    }
-    if (gfeat && pp.ok && options().scatter_variant != 1) {
-        {   // d(feat): LDS-resident planes, no contended global atomics
-            LaunchScope ls(scope_at(flip ? "warp_flipcat_bwd_feat" : "warp_bwd_feat", Hi), st,
-                           sizeof(T) * static_cast<double>(B) * (2.0 * C * Hi * Wi + 2.0 * H * W + (flip ? 2.0 : 1.0) * C * H * W));
+    if (r.feat_planes) {
+        const PlanePlan& pp = r.pp;
+        {
+            LaunchScope ls(scope_at(flip ? "warp_flipcat_bwd_feat" : "warp_bwd_feat", Hi), st, esz * B * (2.0 * C * Hi * Wi + 2.0 * H * W + out_elems));
             const unsigned grid = static_cast<unsigned>(B * pp.groups * pp.nsplit);
-#define FFWM_WARP_PLANE(FL, CG)                                                                              \
-    do {                                                                                                     \
-        auto kfn = warp_bwd_feat_plane_kernel<T, FL, CG>;                                                    \
-        allow_large_lds(reinterpret_cast<const void*>(kfn));                                                 \
-        hipLaunchKernelGGL(kfn, dim3(grid), dim3(kPlaneThreads), pp.lds, st, flow, gout, gfeat, (int)C,      \
-                           (int)Hi, (int)Wi, (int)H, (int)W, pp.groups, pp.nsplit);                          \
-    } while (0)
-#define FFWM_WARP_PLANE_CG(FL)                                                                               \
-    switch (pp.cg) {                                                                                         \
-        case 8: FFWM_WARP_PLANE(FL, 8); break;                                                               \
-        case 4: FFWM_WARP_PLANE(FL, 4); break;                                                               \
-        case 2: FFWM_WARP_PLANE(FL, 2); break;                                                               \
-        default: FFWM_WARP_PLANE(FL, 1); break;                                                              \
-    }
-            if (flip) {
-                FFWM_WARP_PLANE_CG(true)
-            } else {
-                FFWM_WARP_PLANE_CG(false)
-            }
-#undef FFWM_WARP_PLANE_CG
-#undef FFWM_WARP_PLANE
+            if (!dispatch<true, false>(flip, [&](auto FL) {
+                return dispatch<8, 4, 2, 1>(pp.cg, [&](auto CG) {
+                    auto kfn = warp_bwd_feat_plane_kernel<T, FL.value, CG.value>;
+                    allow_large_lds(reinterpret_cast<const void*>(kfn));
+                    hipLaunchKernelGGL(kfn, dim3(grid), dim3(kPlaneThreads), pp.lds, st, flow, gout, gfeat, (int)C, (int)Hi, (int)Wi, (int)H,
+                                       (int)W, pp.groups, pp.nsplit);
+                });
+            })) return no_kernel("ffwm_warp_backward(feat)");
         }
         if (int rc = check_launch("ffwm_warp_backward(feat)")) return rc;
-        if (!gflow) return FFWM_OK;
-        gfeat = nullptr;   // the pixel-major kernel below now only produces d(flow)
     }
     if constexpr (sizeof(T) == 4) {
-        if (gfeat && Hi == H && Wi == W && options().scatter_variant != 1) {
-            // planes beyond LDS, resolution kept: owned tiles + the far complement (no contended global atomics)
-            constexpr int CG = 2;
-            // warp_feat_fixed: 0 = double cells, two channels per group (rounds 3-5, the default); 1 = fixed-point cells on that kernel (900 us:
-            // scratch in the add loop); 3 / 4 = fixed-point cells with a compact per-pixel state (3 registers instead of 10), four / two channels
-            // per group: 551-588 / 498-528 us against the double cells' 474-535 on the same boxes -- the kernel is not bound by its LDS
-            // atomics (profiles/r06_warp_feat_fixed_negative.txt), so all of them stay options
-            const int fixmode = options().warp_feat_fixed;
-            const int cgx = fixmode == 3 ? 4 : CG;        // (4 = the compact kernel with two channels per group)
-            const int ntx = static_cast<int>((W + kWtTile - 1) / kWtTile), nty = static_cast<int>((H + kWtTile - 1) / kWtTile);
-            const int groups = static_cast<int>((C + cgx - 1) / cgx);
-            int gps = groups;                                       // channel groups per block: split until >= 3 blocks per CU
-            while (gps > 1 && B * ntx * nty * ((groups + gps - 1) / gps) < 768) gps = (gps + 1) / 2;
-            // ... and on towards ~12 blocks per CU while a block keeps >= 8 groups: two 8-wave blocks are resident per CU (119 registers),
-            // so 800 blocks of 32 groups ran as two rounds with the second 44 % empty -- [32,64,256,256]: 897 -> 782 us with 8 groups
-            // per block (tools/warp_feat_gps_sweep.py, profiles/r05_warp_feat_gps_sweep.txt; 4: 806, 2: 911)
-            while (gps > 8 && B * ntx * nty * ((groups + gps - 1) / gps) < 3072) gps = (gps + 1) / 2;
-            if (options().warp_feat_gps > 0) gps = options().warp_feat_gps < groups ? options().warp_feat_gps : groups;
-            const int cslabs = (groups + gps - 1) / gps;
-            auto launch_far = [&]() {
-                LaunchScope ls(scope_at(flip ? "warp_flipcat_bwd_feat_far" : "warp_bwd_feat_far", Hi), st, sizeof(T) * static_cast<double>(B) * 2.0 * H * W);
-                const int fx = static_cast<int>((W + kTileX - 1) / kTileX), fy = static_cast<int>((H + kTileY - 1) / kTileY);
-                const unsigned fgrid = static_cast<unsigned>(B * fx * fy);
-                if (flip) hipLaunchKernelGGL((warp_bwd_feat_far_kernel<true>), dim3(fgrid), dim3(kBlock), 0, st, (const float*)flow, (const float*)gout, (float*)gfeat, (int)C, (int)H, (int)W, fx, fy);
-                else hipLaunchKernelGGL((warp_bwd_feat_far_kernel<false>), dim3(fgrid), dim3(kBlock), 0, st, (const float*)flow, (const float*)gout, (float*)gfeat, (int)C, (int)H, (int)W, fx, fy);
-                return check_launch("ffwm_warp_backward(feat, far)");
-            };
-            // (stream order: the far kernel ADDS with global atomics -- in front of the tiles' read-modify-write, behind their plain stores)
-            if (!ovw)
-                if (int rc = launch_far()) return rc;
-            {
-                // algorithmic bytes: the overwriting variant does not read grad_feat
-                LaunchScope ls(scope_at(flip ? "warp_flipcat_bwd_feat_tile" : "warp_bwd_feat_tile", Hi), st,
-                               sizeof(T) * static_cast<double>(B) * ((ovw ? 1.0 : 2.0) * C * Hi * Wi + 2.0 * H * W + (flip ? 2.0 : 1.0) * C * H * W));
-                const unsigned grid = static_cast<unsigned>(B * ntx * nty * cslabs);
-                // 1 = 32-bit fixed-point cells (round 6 experiment, OFF: correct, but hipcc cannot hold the kernel in 128 registers -- 64-104 bytes of
-                // scratch reloaded inside the add loop, each behind an s_waitcnt vmcnt(0): 495 -> 900 us; profiles/r06_warp_feat_fixed_negative.txt)
-                const bool fix = fixmode == 1;
-#define FFWM_WT(FL, OV) do { if (fix) hipLaunchKernelGGL((warp_bwd_feat_tile_kernel<FL, CG, OV, true>), dim3(grid), dim3(kWtThreads), 0, st, (const float*)flow, (const float*)gout, (float*)gfeat, (int)C, (int)H, (int)W, ntx, nty, gps, cslabs); \
-                             else hipLaunchKernelGGL((warp_bwd_feat_tile_kernel<FL, CG, OV, false>), dim3(grid), dim3(kWtThreads), 0, st, (const float*)flow, (const float*)gout, (float*)gfeat, (int)C, (int)H, (int)W, ntx, nty, gps, cslabs); } while (0)
-#define FFWM_WT2(FL, OV) hipLaunchKernelGGL((warp_bwd_feat_tile2_kernel<FL, 4, OV>), dim3(grid), dim3(kWtThreads), 0, st, (const float*)flow, (const float*)gout, (float*)gfeat, (int)C, (int)H, (int)W, ntx, nty, gps, cslabs)
-                if (fixmode == 3) {
-                    if (flip) { if (ovw) FFWM_WT2(true, true); else FFWM_WT2(true, false); }
-                    else { if (ovw) FFWM_WT2(false, true); else FFWM_WT2(false, false); }
-                } else if (fixmode == 4) {
-#define FFWM_WT3(FL, OV) hipLaunchKernelGGL((warp_bwd_feat_tile2_kernel<FL, 2, OV>), dim3(grid), dim3(kWtThreads), 0, st, (const float*)flow, (const float*)gout, (float*)gfeat, (int)C, (int)H, (int)W, ntx, nty, gps, cslabs)
-                    if (flip) { if (ovw) FFWM_WT3(true, true); else FFWM_WT3(true, false); }
-                    else { if (ovw) FFWM_WT3(false, true); else FFWM_WT3(false, false); }
-#undef FFWM_WT3
-                } else if (flip) { if (ovw) FFWM_WT(true, true); else FFWM_WT(true, false); }
-                else { if (ovw) FFWM_WT(false, true); else FFWM_WT(false, false); }
-#undef FFWM_WT2
-#undef FFWM_WT
-            }
-            if (int rc = check_launch("ffwm_warp_backward(feat, tiles)")) return rc;
-            if (ovw)
-                if (int rc = launch_far()) return rc;
-            if (!gflow) return FFWM_OK;
-            gfeat = nullptr;
+        if (r.feat_tiles) {
+            int rc = FFWM_OK;
+            select_warp_feat_tile(options().warp_feat_fixed, [&](auto cfg) {
+                using Cfg = decltype(cfg);
+                const int ntx = static_cast<int>((W + kWtTile - 1) / kWtTile), nty = static_cast<int>((H + kWtTile - 1) / kWtTile);
+                const int groups = static_cast<int>((C + Cfg::CG - 1) / Cfg::CG);
+                // channel groups per block: split until >= 3 blocks per CU
+                int gps = halve_slab(groups, groups, B * ntx * nty, 768, 1);
+                // ... and on towards ~12 blocks per CU while a block keeps >= 8 groups: two 8-wave blocks are resident per CU (119 registers),
+                // so 800 blocks of 32 groups ran as two rounds with the second 44 % empty -- [32,64,256,256]: 897 -> 782 us with 8 groups
+                // per block (tools/warp_feat_gps_sweep.py, profiles/r05_warp_feat_gps_sweep.txt; 4: 806, 2: 911)
+                gps = halve_slab(gps, groups, B * ntx * nty, 3072, 8);
+                if (options().warp_feat_gps > 0) gps = options().warp_feat_gps < groups ? options().warp_feat_gps : groups;
+                const int cslabs = (groups + gps - 1) / gps;
+                auto launch_far = [&]() {
+                    LaunchScope ls(scope_at(flip ? "warp_flipcat_bwd_feat_far" : "warp_bwd_feat_far", Hi), st, esz * B * 2.0 * H * W);
+                    const int fx = static_cast<int>((W + kTileX - 1) / kTileX), fy = static_cast<int>((H + kTileY - 1) / kTileY);
+                    const unsigned fgrid = static_cast<unsigned>(B * fx * fy);
+                    dispatch<true, false>(flip, [&](auto FL) {
+                        hipLaunchKernelGGL((warp_bwd_feat_far_kernel<FL.value>), dim3(fgrid), dim3(kBlock), 0, st, (const float*)flow,
+                                           (const float*)gout, (float*)gfeat, (int)C, (int)H, (int)W, fx, fy);
+                    });
+                    return check_launch("ffwm_warp_backward(feat, far)");
+                };
+                // (stream order: the far kernel ADDS with global atomics -- in front of the tiles' read-modify-write, behind their plain stores)
+                if (!r.overwrite && (rc = launch_far())) return;
+                {
+                    // algorithmic bytes: the overwriting variant does not read grad_feat
+                    LaunchScope ls(scope_at(flip ? "warp_flipcat_bwd_feat_tile" : "warp_bwd_feat_tile", Hi), st,
+                                   esz * B * ((r.overwrite ? 1.0 : 2.0) * C * Hi * Wi + 2.0 * H * W + out_elems));
+                    const unsigned grid = static_cast<unsigned>(B * ntx * nty * cslabs);
+                    dispatch<true, false>(flip, [&](auto FL) {
+                        dispatch<true, false>(r.overwrite, [&](auto OV) {
+                            auto launch = [&](auto kfn) {
+                                hipLaunchKernelGGL(kfn, dim3(grid), dim3(kWtThreads), 0, st, (const float*)flow, (const float*)gout, (float*)gfeat,
+                                                   (int)C, (int)H, (int)W, ntx, nty, gps, cslabs);
+                            };
+                            if constexpr (Cfg::COMPACT) launch(warp_bwd_feat_tile2_kernel<FL.value, Cfg::CG, OV.value>);
+                            else launch(warp_bwd_feat_tile_kernel<FL.value, Cfg::CG, OV.value, Cfg::FIXED>);
+                        });
+                    });
+                }
+                if ((rc = check_launch("ffwm_warp_backward(feat, tiles)"))) return;
+                if (r.overwrite) rc = launch_far();
+            });
+            if (rc) return rc;
         }
-    }
-    if constexpr (sizeof(T) == 4) {
-        // d(flow) alone on LDS-staged tiles (warp_bwd_flow_lds_body) for the same tensors the forward takes there; warp_multi_lds = 1: never
-        const int variant = options().warp_fwd_variant;
-        if (!gfeat && gflow && options().warp_multi_lds != 1 &&
-            (variant == 2 || (variant == 0 && H >= 64 && W >= 64 && B * C * H * W >= (1LL << 24)))) {
-            const int txs = static_cast<int>((W + kWlTileX - 1) / kWlTileX), tys = static_cast<int>((H + kWlTileY - 1) / kWlTileY);
+        if (r.flow_lds) {
             // measured at [32,64,256,256] (tools/warp_bwd_flow_variants.py): slab 8 / 16 / 32 / 64 -> 492 / 375 / 330 / 310 us (direct: 423)
-            int cs = options().channel_slab > 0 ? options().channel_slab : 64;
-            if (cs > C) cs = static_cast<int>(C);
-            while (cs > 8 && B * txs * tys * ((C + cs - 1) / cs) < 2048) cs = (cs + 1) / 2;
-            const int cslabs = static_cast<int>((C + cs - 1) / cs);
-            const unsigned grid = static_cast<unsigned>(B * txs * tys * cslabs);
-            LaunchScope ls(scope_at(flip ? "warp_flipcat_bwd_flow" : "warp_bwd_flow", H), st,
-                           sizeof(T) * static_cast<double>(B) * (static_cast<double>(C) * Hi * Wi + 4.0 * H * W + (flip ? 2.0 : 1.0) * C * H * W));
-            if (flip)
-                hipLaunchKernelGGL((warp_bwd_flow_lds_kernel<true>), dim3(grid), dim3(kBlock), 0, st, (const float*)feat, (const float*)flow,
-                                   (const float*)gout, (float*)gflow, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, txs, tys, cslabs, cs, remap);
-            else
-                hipLaunchKernelGGL((warp_bwd_flow_lds_kernel<false>), dim3(grid), dim3(kBlock), 0, st, (const float*)feat, (const float*)flow,
-                                   (const float*)gout, (float*)gflow, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, txs, tys, cslabs, cs, remap);
+            const LdsTiles t = plan_lds_tiles(B, C, H, W, 64, 8, 2048);
+            LaunchScope ls(scope_at(flip ? "warp_flipcat_bwd_flow" : "warp_bwd_flow", H), st, bytes_flow);
+            dispatch<true, false>(flip, [&](auto FL) {
+                hipLaunchKernelGGL((warp_bwd_flow_lds_kernel<FL.value>), dim3(t.grid), dim3(kBlock), 0, st, (const float*)feat, (const float*)flow,
+                                   (const float*)gout, (float*)gflow, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, t.txs, t.tys, t.cslabs, t.cs, remap);
+            });
             return check_launch("ffwm_warp_backward(flow, lds)");
         }
     }
+    if (!r.feat_pixels && !r.flow_pixels) return FFWM_OK;
+    T* const gfeat_px = r.feat_pixels ? gfeat : nullptr;
     const Geometry g = plan(B, C, H, W, 32);
-    LaunchScope ls(scope_at(gfeat ? (flip ? "warp_flipcat_bwd" : "warp_bwd") : (flip ? "warp_flipcat_bwd_flow" : "warp_bwd_flow"), H), st,
-                   gfeat ? bytes : sizeof(T) * static_cast<double>(B) * (static_cast<double>(C) * Hi * Wi + 4.0 * H * W + (flip ? 2.0 : 1.0) * C * H * W));
-    if (flip)
-        hipLaunchKernelGGL((warp_bwd_kernel<T, true>), dim3(g.grid), dim3(kBlock), 0, st, feat, flow, gout,
-                           gfeat, gflow, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, g.tiles_x, g.tiles_y,
-                           g.cslabs, g.cs, remap);
-    else
-        hipLaunchKernelGGL((warp_bwd_kernel<T, false>), dim3(g.grid), dim3(kBlock), 0, st, feat, flow, gout,
-                           gfeat, gflow, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, g.tiles_x, g.tiles_y,
-                           g.cslabs, g.cs, remap);
+    LaunchScope ls(scope_at(gfeat_px ? (flip ? "warp_flipcat_bwd" : "warp_bwd") : (flip ? "warp_flipcat_bwd_flow" : "warp_bwd_flow"), H), st,
+                   gfeat_px ? esz * B * (2.0 * C * Hi * Wi + 4.0 * H * W + out_elems) : bytes_flow);
+    dispatch<true, false>(flip, [&](auto FL) {
+        hipLaunchKernelGGL((warp_bwd_kernel<T, FL.value>), dim3(g.grid), dim3(kBlock), 0, st, feat, flow, gout, gfeat_px, gflow,
+                           (int)C, (int)Hi, (int)Wi, (int)H, (int)W, g.tiles_x, g.tiles_y, g.cslabs, g.cs, remap);
+    });
     return check_launch("ffwm_warp_backward");
-}
-
-
-inline bool fwd_wants_lds(int64_t B, int64_t C, int64_t H, int64_t W, size_t esz) {
-    const int variant = options().warp_fwd_variant;
-    return esz == 4 && (variant == 2 || (variant == 0 && H >= 64 && W >= 64 && B * C * H * W >= (1LL << 24)));
 }
 
 // A problem of a multi FORWARD launch on LDS-staged tiles?  warp_multi_lds: 0 = auto (float, planes of >= 32 x 32 output pixels with
@@ -1716,13 +1723,9 @@ inline void fill_problem(WarpProblem& q, const ffwm_warp_problem& pr, int cs_def
     q.begin = begin;
     q.lds = lds ? 1 : 0;
     if (lds) {
-        const int txs = static_cast<int>((pr.W + kWlTileX - 1) / kWlTileX), tys = static_cast<int>((pr.H + kWlTileY - 1) / kWlTileY);
-        int cs = options().channel_slab > 0 ? options().channel_slab : 16;
-        if (cs > pr.C) cs = static_cast<int>(pr.C);
-        while (cs > 4 && pr.B * txs * tys * ((pr.C + cs - 1) / cs) < 1024) cs = (cs + 1) / 2;     // >= 4 tiles per CU for the problem
-        q.tiles_x = txs; q.tiles_y = tys; q.cs = cs;
-        q.cslabs = static_cast<int>((pr.C + cs - 1) / cs);
-        q.nblk = static_cast<unsigned>(pr.B * txs * tys * q.cslabs);
+        const LdsTiles t = plan_lds_tiles(pr.B, pr.C, pr.H, pr.W, 16, 4, 1024);     // >= 4 tiles per CU for the problem
+        q.tiles_x = t.txs; q.tiles_y = t.tys; q.cs = t.cs; q.cslabs = t.cslabs;
+        q.nblk = t.grid;
         return;
     }
     const Geometry g = plan(pr.B, pr.C, pr.H, pr.W, cs_default);
@@ -1753,8 +1756,9 @@ int launch_fwd_multi(const ffwm_warp_problem* probs, int n, int flip, hipStream_
         if (tab.n == 0) return FFWM_OK;
         {
             LaunchScope ls(flip ? "warp_flipcat_fwd_multi" : "warp_fwd_multi", st, bytes);
-            if (flip) hipLaunchKernelGGL((warp_fwd_multi_kernel<T, true>), dim3(blocks), dim3(kBlock), 0, st, tab);
-            else hipLaunchKernelGGL((warp_fwd_multi_kernel<T, false>), dim3(blocks), dim3(kBlock), 0, st, tab);
+            dispatch<true, false>(flip != 0, [&](auto FL) {
+                hipLaunchKernelGGL((warp_fwd_multi_kernel<T, FL.value>), dim3(blocks), dim3(kBlock), 0, st, tab);
+            });
         }
         tab.n = 0; blocks = 0; bytes = 0;
         return check_launch("ffwm_warp_multi_forward");
@@ -1798,20 +1802,13 @@ int launch_bwd_multi(const ffwm_warp_problem* probs, int n, int flip, hipStream_
                 }
                 {
                     LaunchScope ls(flip ? "warp_flipcat_bwd_feat_multi" : "warp_bwd_feat_multi", st, bytes);
-#define FFWM_PLANE_MULTI(FL, CGV)                                                                                  \
-    do {                                                                                                           \
-        auto kfn = warp_bwd_feat_plane_multi_kernel<T, FL, CGV>;                                                   \
-        allow_large_lds(reinterpret_cast<const void*>(kfn));                                                       \
-        hipLaunchKernelGGL(kfn, dim3(blocks), dim3(kPlaneThreads), lds, st, tab);                                  \
-    } while (0)
-                    if (flip) {
-                        switch (cg) { case 8: FFWM_PLANE_MULTI(true, 8); break; case 4: FFWM_PLANE_MULTI(true, 4); break;
-                                      case 2: FFWM_PLANE_MULTI(true, 2); break; default: FFWM_PLANE_MULTI(true, 1); break; }
-                    } else {
-                        switch (cg) { case 8: FFWM_PLANE_MULTI(false, 8); break; case 4: FFWM_PLANE_MULTI(false, 4); break;
-                                      case 2: FFWM_PLANE_MULTI(false, 2); break; default: FFWM_PLANE_MULTI(false, 1); break; }
-                    }
-#undef FFWM_PLANE_MULTI
+                    if (!dispatch<true, false>(flip != 0, [&](auto FL) {
+                        return dispatch<8, 4, 2, 1>(cg, [&](auto CG) {
+                            auto kfn = warp_bwd_feat_plane_multi_kernel<T, FL.value, CG.value>;
+                            allow_large_lds(reinterpret_cast<const void*>(kfn));
+                            hipLaunchKernelGGL(kfn, dim3(blocks), dim3(kPlaneThreads), lds, st, tab);
+                        });
+                    })) return no_kernel("ffwm_warp_multi_backward(feat, planes)");
                 }
                 for (int m : members) done[m] = true;
                 tab.n = 0; blocks = 0; lds = 0; bytes = 0; members.clear();
@@ -1855,8 +1852,9 @@ int launch_bwd_multi(const ffwm_warp_problem* probs, int n, int flip, hipStream_
         if (tab.n == 0) return FFWM_OK;
         {
             LaunchScope ls(flip ? "warp_flipcat_bwd_flow_multi" : "warp_bwd_flow_multi", st, bytes);
-            if (flip) hipLaunchKernelGGL((warp_bwd_flow_multi_kernel<T, true>), dim3(blocks), dim3(kBlock), 0, st, tab);
-            else hipLaunchKernelGGL((warp_bwd_flow_multi_kernel<T, false>), dim3(blocks), dim3(kBlock), 0, st, tab);
+            dispatch<true, false>(flip != 0, [&](auto FL) {
+                hipLaunchKernelGGL((warp_bwd_flow_multi_kernel<T, FL.value>), dim3(blocks), dim3(kBlock), 0, st, tab);
+            });
         }
         tab.n = 0; blocks = 0; bytes = 0;
         return check_launch("ffwm_warp_multi_backward(flow)");
@@ -1887,12 +1885,10 @@ extern "C" int ffwm_warp_forward(const void* feat, const void* flow, void* outpu
     const char* fn = "ffwm_warp_forward";
     FFWM_REQUIRE(feat && flow && output, FFWM_ERR_ARG, "%s: NULL tensor pointer", fn);
     if (int rc = check_dims(fn, B, C, Hi, Wi, H, W, dtype)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == FFWM_F32)
-        return launch_fwd<float>((const float*)feat, (const float*)flow, (float*)output, B, C, Hi, Wi, H, W,
-                                 flipcat, st);
-    return launch_fwd<double>((const double*)feat, (const double*)flow, (double*)output, B, C, Hi, Wi, H, W,
-                              flipcat, st);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_fwd<T>((const T*)feat, (const T*)flow, (T*)output, B, C, Hi, Wi, H, W, flipcat, static_cast<hipStream_t>(stream));
+    });
 }
 
 extern "C" int ffwm_warp_backward(const void* feat, const void* flow, const void* grad_output,
@@ -1902,12 +1898,11 @@ extern "C" int ffwm_warp_backward(const void* feat, const void* flow, const void
     FFWM_REQUIRE(feat && flow && grad_output, FFWM_ERR_ARG, "%s: NULL tensor pointer", fn);
     if (int rc = check_dims(fn, B, C, Hi, Wi, H, W, dtype)) return rc;
     if (!grad_feat && !grad_flow) return FFWM_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == FFWM_F32)
-        return launch_bwd<float>((const float*)feat, (const float*)flow, (const float*)grad_output,
-                                 (float*)grad_feat, (float*)grad_flow, B, C, Hi, Wi, H, W, flipcat, st);
-    return launch_bwd<double>((const double*)feat, (const double*)flow, (const double*)grad_output,
-                              (double*)grad_feat, (double*)grad_flow, B, C, Hi, Wi, H, W, flipcat, st);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_bwd<T>((const T*)feat, (const T*)flow, (const T*)grad_output, (T*)grad_feat, (T*)grad_flow, B, C, Hi, Wi, H, W, flipcat,
+                             static_cast<hipStream_t>(stream));
+    });
 }
 
 extern "C" int ffwm_warp_multi_forward(const ffwm_warp_problem* problems, int n, int flipcat, int dtype, void* stream) {
@@ -1917,8 +1912,7 @@ extern "C" int ffwm_warp_multi_forward(const ffwm_warp_problem* problems, int n,
         FFWM_REQUIRE(problems[i].feat && problems[i].flow && problems[i].output, FFWM_ERR_ARG, "%s: NULL tensor pointer in problem %d", fn, i);
         if (int rc = check_dims(fn, problems[i].B, problems[i].C, problems[i].Hi, problems[i].Wi, problems[i].H, problems[i].W, dtype)) return rc;
     }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    return dtype == FFWM_F32 ? launch_fwd_multi<float>(problems, n, flipcat, st) : launch_fwd_multi<double>(problems, n, flipcat, st);
+    return by_dtype(dtype, [&](auto t) { return launch_fwd_multi<decltype(t)>(problems, n, flipcat, static_cast<hipStream_t>(stream)); });
 }
 
 extern "C" int ffwm_warp_multi_backward(const ffwm_warp_problem* problems, int n, int flipcat, int dtype, void* stream) {
@@ -1928,6 +1922,5 @@ extern "C" int ffwm_warp_multi_backward(const ffwm_warp_problem* problems, int n
         FFWM_REQUIRE(problems[i].feat && problems[i].flow && problems[i].grad_output, FFWM_ERR_ARG, "%s: NULL tensor pointer in problem %d", fn, i);
         if (int rc = check_dims(fn, problems[i].B, problems[i].C, problems[i].Hi, problems[i].Wi, problems[i].H, problems[i].W, dtype)) return rc;
     }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    return dtype == FFWM_F32 ? launch_bwd_multi<float>(problems, n, flipcat, st) : launch_bwd_multi<double>(problems, n, flipcat, st);
+    return by_dtype(dtype, [&](auto t) { return launch_bwd_multi<decltype(t)>(problems, n, flipcat, static_cast<hipStream_t>(stream)); });
 }

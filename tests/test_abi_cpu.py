@@ -88,6 +88,37 @@ def test_argument_errors_are_reported_before_launch(hiplib):
     assert rc == -1
 
 
+# every key of ffwm_set_option with its default (csrc/common.hpp generates struct Options and the key table from one list)
+OPTION_DEFAULTS = [
+    ("be_fwd_variant", 0), ("be_bwd_variant", 0), ("channel_slab", 0), ("xcd_remap", 1), ("scatter_variant", 0),
+    ("rows_per_thread", 0), ("warp_fwd_variant", 0), ("be_bwd_halo", 0), ("be_bwd_rows", 0), ("rs_fwd_variant", 0),
+    ("rs_bwd1_variant", 0), ("conv_tile_variant", 0), ("conv_wino_raw", 1), ("conv_fwd_split_target", 0),
+    ("conv_wgrad_slice_target", 0), ("conv_wino_ws", 0), ("conv_wino_split", 1), ("conv_thin_tail", 1), ("warp_nt", 0),
+    ("warp_pair_loads", 1), ("conv_wgrad_wino", 0), ("warp_multi_planes", 0), ("warp_multi_lds", 0), ("warp_multi_order", 0),
+    ("conv_fwd_kfast", 1), ("warp_feat_gps", 0), ("rs_bwd1_rpt", 0), ("rs_bwd1_fixed", 0), ("be_bwd_fixed", 0),
+    ("rs_bwd1_owned", 0), ("rs_bwd1_owned_min_pixels", 0), ("rs_bwd1_owned_blocks", 0), ("warp_feat_fixed", 0),
+    ("conv_thin_variant", 0), ("ba_fwd_pix", 1), ("ba_bwd_fused", 3), ("ba_bwd_pix", 4), ("be_bwd_flush", 0),
+    ("zero_fill_memset", 0), ("conv_wgrad_unsliced", 0),
+]
+
+
+def test_option_table_keys_and_defaults(hiplib):
+    """Setting every option to its documented default returns that default in a process that has set nothing: a fresh interpreter
+    loads the library and walks the literal list above (this process may have changed options in other tests)."""
+    import subprocess
+    import sys
+    assert len(OPTION_DEFAULTS) == len(set(k for k, _ in OPTION_DEFAULTS)) == 40
+    assert "FFWM_OPTS" not in os.environ, "FFWM_OPTS is set: the library would not start from its defaults"
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "from ffwm_amd import _lib\n"
+            "lib = _lib.load()\n"
+            "bad = [(k, d, lib.ffwm_set_option(k.encode(), d)) for k, d in %r]\n"
+            "bad = [b for b in bad if b[2] != b[1]]\n"
+            "assert not bad, bad\n" % (ROOT, OPTION_DEFAULTS))
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+
+
 def test_cpu_tensors_are_refused_like_the_reference():
     # /root/reference/models/external_function.py:37-38,84-85 raise NotImplementedError on CPU
     from ffwm_amd import external_function as E
