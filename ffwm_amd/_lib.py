@@ -67,6 +67,8 @@ _SIGNATURES = {
     "ffwm_affine_regularization": [_p, _p, _p, _p, _i64, _i64, _i64, _i, ctypes.c_double, _i, _p],
     "ffwm_correlation_colmax": [_p, _p, _p, _i64, _i64, _i64, _i, _p],
     "ffwm_guided_filter_backward": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i, _i, _p],
+    "ffwm_guided_filter_forward_general": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, ctypes.c_double, _i, _p],
+    "ffwm_guided_filter_backward_general": [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, _i, _p],
     "ffwm_l1_multi": [_p, _i, _p, _p, _i, _i, _p],          # (array of ffwm_l1_problem, n, out, grad_out, n_slots, dtype, stream)
     "ffwm_conv3x3_winograd_weights_multi": [_p, _i, _i, _p],      # (array of ffwm_wino_weights, n, dtype, stream)
     "ffwm_prof_enable": [_i],
@@ -82,7 +84,7 @@ _SIGNATURES = {
 }
 
 EXPORTS = sorted(list(_SIGNATURES) + ["ffwm_last_error", "ffwm_conv3x3_winograd_workspace_bytes", "ffwm_conv3x3_winograd_splits",
-                                      "ffwm_conv2d_forward_workspace"])
+                                      "ffwm_conv2d_forward_workspace", "ffwm_guided_filter_workspace_bytes"])
 
 
 class FFWMError(RuntimeError):
@@ -109,6 +111,8 @@ def load():
     lib.ffwm_conv3x3_winograd_splits.restype = _i
     lib.ffwm_conv2d_forward_workspace.argtypes = [_i64] * 5 + [_i] * 4
     lib.ffwm_conv2d_forward_workspace.restype = _i64
+    lib.ffwm_guided_filter_workspace_bytes.argtypes = [_i64] * 4 + [_i, _i]
+    lib.ffwm_guided_filter_workspace_bytes.restype = _i64
     lib.ffwm_last_error.argtypes = []
     lib.ffwm_last_error.restype = ctypes.c_char_p
     got = lib.ffwm_abi_version()

@@ -317,9 +317,10 @@ class WarpFlipCat(nn.Module):
 
 
 class GuidedFilterFunction(Function):
-    """apply(x[B,C,H,W], y[B,C,H,W], r, eps) -> GuidedFilter(r, eps)(x, y) of the reference
-    (models/external_function.py:239-277), four launches forward and four backward (separable column / row passes over the whole chip).  y is data (FFWM filters
-    the generated image against the ground truth, models/ffwm_model.py:81): it gets no gradient."""
+    """apply(x[B,1 or C,H,W], y[B,C,H,W], r, eps) -> GuidedFilter(r, eps)(x, y) of the reference
+    (models/external_function.py:239-277), differentiable in x and y.  FFWM's own call (c_x == c_y, planes up to 128 x 128, y the
+    ground truth: models/ffwm_model.py:81) is four launches forward and four backward; longer lines, a one-channel guide and the
+    gradient for y take the general passes of csrc/guided_filter.hip (five and four launches)."""
 
     @staticmethod
     def forward(ctx, x, y, r, eps):
@@ -333,16 +334,15 @@ class GuidedFilterFunction(Function):
 
     @staticmethod
     def backward(ctx, grad_output):
-        if ctx.needs_input_grad[1]:
-            raise NotImplementedError("GuidedFilterFunction: no gradient for y (the guidance target is data)")
         x, y, saved = ctx.saved_tensors
-        gx = ops.guided_filter_backward(x, y, saved, grad_output.contiguous(), ctx.r) if ctx.needs_input_grad[0] else None
-        return gx, None, None, None
+        gx, gy = ops.guided_filter_backward_xy(x, y, saved, grad_output.contiguous(), ctx.r,
+                                               want_x=ctx.needs_input_grad[0], want_y=ctx.needs_input_grad[1])
+        return gx, gy, None, None
 
 
 class GuidedFilter(nn.Module):
-    """Same constructor and call as the reference's GuidedFilter(r, eps=1e-8)(x, y)
-    (models/external_function.py:239-277) for c_x == c_y, H, W <= 128."""
+    """Same constructor, call and assertions as the reference's GuidedFilter(r, eps=1e-8)(x, y)
+    (models/external_function.py:239-277)."""
 
     def __init__(self, r, eps=1e-8):
         super().__init__()
@@ -353,8 +353,7 @@ class GuidedFilter(nn.Module):
         n_x, c_x, h_x, w_x = x.size()
         n_y, c_y, h_y, w_y = y.size()
         assert n_x == n_y
+        assert c_x == 1 or c_x == c_y
         assert h_x == h_y and w_x == w_y
         assert h_x > 2 * self.r + 1 and w_x > 2 * self.r + 1
-        if c_x != c_y:
-            raise NotImplementedError("GuidedFilter: the HIP kernel needs c_x == c_y (FFWM's only usage)")
         return GuidedFilterFunction.apply(x, y, self.r, self.eps)

@@ -367,37 +367,75 @@ def warp_multi_backward(feats, flows, grad_outputs, flipcat, grad_feats, grad_fl
 
 
 # ---------------------------------------------------------------- guided filter
+def _gf_shapes(name, x, y):
+    """(B, Cx, Cy, H, W) of a guided-filter call; c_x == 1 or c_x == c_y as the reference asserts (external_function.py:246-249)."""
+    if x.size(0) != y.size(0) or x.shape[2:] != y.shape[2:] or x.size(1) not in (1, y.size(1)):
+        raise ValueError("%s: x and y must agree in N, H, W, with c_x == 1 or c_x == c_y, got %s vs %s"
+                         % (name, tuple(x.shape), tuple(y.shape)))
+    return x.size(0), x.size(1), y.size(1), x.size(2), x.size(3)
+
+
+def _gf_workspace(x, B, Cx, Cy, H, W, backward):
+    n = _lib.load().ffwm_guided_filter_workspace_bytes(B * Cx, B * Cy, H, W, _dtype_code(x), 1 if backward else 0)
+    _lib.check(min(n, 0), "ffwm_guided_filter_workspace_bytes")
+    return x.new_empty(n // x.element_size())
+
+
+_GF_FAST = 128      # H, W up to here with c_x == c_y: the four-launch kernels, no workspace forward
+
+
 def guided_filter_forward(x, y, r, eps=1e-8):
-    """-> (out, saved); GuidedFilter(r, eps)(x, y), reference external_function.py:239-277."""
+    """-> (out, saved); GuidedFilter(r, eps)(x, y), reference external_function.py:239-277: x [B, 1 or C, H, W], y [B, C, H, W].
+    saved is [5, B, C, H, W] for c_x == c_y and a flat buffer (2 B + 3 B C planes) for a one-channel guide."""
     _check("guided_filter_forward", x, y)
-    if x.shape != y.shape:
-        raise ValueError("guided_filter_forward: x and y must have the same shape (c_x == c_y), got %s vs %s"
-                         % (tuple(x.shape), tuple(y.shape)))
-    B, C, H, W = x.shape
-    out = torch.empty_like(x)
-    saved = x.new_empty((5, B, C, H, W))
+    B, Cx, Cy, H, W = _gf_shapes("guided_filter_forward", x, y)
+    out = torch.empty_like(y)
+    saved = x.new_empty((5, B, Cy, H, W)) if Cx == Cy else x.new_empty(((2 * Cx + 3 * Cy) * B * H * W,))
     if out.numel() == 0:
         return out, saved
     with _on_device(x) as stream:
-        _lib.check(_lib.load().ffwm_guided_filter_forward(
-            _ptr(x), _ptr(y), _ptr(out), _ptr(saved), B * C, H, W, int(r), float(eps), _dtype_code(x), stream),
-            "ffwm_guided_filter_forward")
+        if Cx == Cy and H <= _GF_FAST and W <= _GF_FAST:
+            _lib.check(_lib.load().ffwm_guided_filter_forward(
+                _ptr(x), _ptr(y), _ptr(out), _ptr(saved), B * Cy, H, W, int(r), float(eps), _dtype_code(x), stream),
+                "ffwm_guided_filter_forward")
+        else:
+            ws = _gf_workspace(x, B, Cx, Cy, H, W, False)
+            _lib.check(_lib.load().ffwm_guided_filter_forward_general(
+                _ptr(x), _ptr(y), _ptr(out), _ptr(saved), _ptr(ws), B * Cx, B * Cy, H, W, int(r), float(eps), _dtype_code(x),
+                stream), "ffwm_guided_filter_forward_general")
     return out, saved
 
 
-def guided_filter_backward(x, y, saved, grad_output, r):
-    """-> grad_x (y is data and gets no gradient)."""
+def guided_filter_backward_xy(x, y, saved, grad_output, r, want_x=True, want_y=True):
+    """-> (grad_x, grad_y), None for the one that is not wanted (it is neither computed nor written).  grad_x of a one-channel
+    guide is the sum over y's channels."""
     _check("guided_filter_backward", x, y, grad_output)
-    B, C, H, W = x.shape
-    gx = torch.empty_like(x)
-    if gx.numel() == 0:
-        return gx
-    ws = x.new_empty((2, B, C, H, W))
+    B, Cx, Cy, H, W = _gf_shapes("guided_filter_backward", x, y)
+    if grad_output.shape != y.shape:
+        raise ValueError("guided_filter_backward: grad_output must have y's shape")
+    if saved.dtype != x.dtype or saved.device != x.device or saved.numel() != (2 * Cx + 3 * Cy) * B * H * W:
+        raise ValueError("guided_filter_backward: saved is not what guided_filter_forward returned for these tensors")
+    gx = torch.empty_like(x) if want_x else None
+    gy = torch.empty_like(y) if want_y else None
+    if y.numel() == 0 or not (want_x or want_y):
+        return gx, gy
     with _on_device(x) as stream:
-        _lib.check(_lib.load().ffwm_guided_filter_backward(
-            _ptr(x), _ptr(y), _ptr(saved), _ptr(grad_output), _ptr(gx), _ptr(ws), B * C, H, W, int(r), _dtype_code(x), stream),
-            "ffwm_guided_filter_backward")
-    return gx
+        if Cx == Cy and H <= _GF_FAST and W <= _GF_FAST and not want_y:
+            ws = x.new_empty((2, B, Cy, H, W))
+            _lib.check(_lib.load().ffwm_guided_filter_backward(
+                _ptr(x), _ptr(y), _ptr(saved), _ptr(grad_output), _ptr(gx), _ptr(ws), B * Cy, H, W, int(r), _dtype_code(x), stream),
+                "ffwm_guided_filter_backward")
+        else:
+            ws = _gf_workspace(x, B, Cx, Cy, H, W, True)
+            _lib.check(_lib.load().ffwm_guided_filter_backward_general(
+                _ptr(x), _ptr(y), _ptr(saved), _ptr(grad_output), _ptr(gx), _ptr(gy), _ptr(ws), B * Cx, B * Cy, H, W, int(r),
+                _dtype_code(x), stream), "ffwm_guided_filter_backward_general")
+    return gx, gy
+
+
+def guided_filter_backward(x, y, saved, grad_output, r):
+    """-> grad_x alone (guided_filter_backward_xy for grad_y)."""
+    return guided_filter_backward_xy(x, y, saved, grad_output, r, True, False)[0]
 
 
 # ---------------------------------------------------------------- fused affine regularisation

@@ -243,8 +243,8 @@ int ffwm_spectral_norm_backward(const ffwm_sn_grad_layer* layers, int n_layers, 
 /* ---- guided filter (illumination-adaption path) ------------------------------------------------
  * out = GuidedFilter(r, eps)(x, y) of models/external_function.py:239-277 (box filters as cumsum
  * differences, :164-193), per [H, W] plane; x, y, out are [planes = B*C, H, W] contiguous with
- * c_x == c_y (the only way FFWM calls it: models/ffwm_model.py:57-59,81,104-105).  H, W <= 128,
- * H > 2r+1, W > 2r+1.  `saved` [5, planes, H, W] receives mean_x, mean_y, A, var_x+eps, mean_A for the
+ * c_x == c_y (the only way FFWM calls it: models/ffwm_model.py:57-59,81,104-105).  H, W <= 128
+ * (these argument lists carry no workspace for longer lines: ffwm_guided_filter_*_general below), H > 2r+1, W > 2r+1.  `saved` [5, planes, H, W] receives mean_x, mean_y, A, var_x+eps, mean_A for the
  * backward.  Four launches (column pass / row pass + pointwise stage, twice), each over planes x W/32 x quantities or
  * planes x H/4 workgroups; the PyTorch module issues ~100. */
 int ffwm_guided_filter_forward(const void* x, const void* y, void* output, void* saved,
@@ -256,6 +256,30 @@ int ffwm_guided_filter_forward(const void* x, const void* y, void* output, void*
 int ffwm_guided_filter_backward(const void* x, const void* y, const void* saved,
                                 const void* grad_output, void* grad_x, void* workspace,
                                 int64_t planes, int64_t H, int64_t W, int r, int dtype, void* stream);
+
+/* The reference's whole contract (models/external_function.py:239-277): planes of any size (H, W <= 8192 and H W < 2^28, else
+ * FFWM_ERR_SIZE), a guide of one channel broadcast over the channels of y, and the gradient for y.
+ *   x [planes_x, H, W], y / output / grad_output [planes_y, H, W] with planes_y = planes_x * k: k = 1 is c_x == c_y, k = c_y is the
+ *   one-channel guide (x plane p guides the y planes p k .. p k + k - 1, i.e. x [B,1,H,W] against y [B,C,H,W]).
+ *   saved: 2 planes_x + 3 planes_y planes of H W elements: mean_x [planes_x], mean_y, A [planes_y], var_x+eps [planes_x], mean_A
+ *   [planes_y] -- for k = 1 the [5, planes, H, W] of the entry points above, which may then be mixed with these.
+ *   workspace: ffwm_guided_filter_workspace_bytes(planes_x, planes_y, H, W, dtype, backward) bytes (a negative ffwm_status for
+ *   arguments the entry points refuse), contents irrelevant on entry and exit; 0 bytes (NULL allowed) for a forward call that the
+ *   kernels above serve.
+ *   backward: grad_x [planes_x, H, W] (summed over the k channels, channel 0 first) and grad_y [planes_y, H, W] are OVERWRITTEN;
+ *   either may be NULL and is then neither computed nor written, but not both.
+ * Calls that the four-launch kernels above serve (k = 1, H, W <= 128, no grad_y) run on them unchanged; everything else takes five
+ * launches forward and four backward of wave-per-chunk sliding-window passes (csrc/guided_filter.hip, "the general path").
+ * No atomics, no host synchronisation, bit-identical from run to run. */
+int64_t ffwm_guided_filter_workspace_bytes(int64_t planes_x, int64_t planes_y, int64_t H, int64_t W,
+                                           int dtype, int backward);
+int ffwm_guided_filter_forward_general(const void* x, const void* y, void* output, void* saved,
+                                       void* workspace, int64_t planes_x, int64_t planes_y, int64_t H,
+                                       int64_t W, int r, double eps, int dtype, void* stream);
+int ffwm_guided_filter_backward_general(const void* x, const void* y, const void* saved,
+                                        const void* grad_output, void* grad_x, void* grad_y,
+                                        void* workspace, int64_t planes_x, int64_t planes_y, int64_t H,
+                                        int64_t W, int r, int dtype, void* stream);
 
 /* ---- fused affine regularisation (FlowNet pre-training) -----------------------------------------
  * AffineRegularizationLoss.__call__ of models/losses.py:200-219 for one flow scale in ONE launch:
