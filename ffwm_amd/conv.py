@@ -1,21 +1,31 @@
-"""Routing of conv weight gradients to the hand-written MFMA kernel (csrc/conv_wgrad.hip).
+"""Routing of the networks' convolutions to the library's own MFMA kernels.
 
-The conv stacks of the reference (models/base_networks.py:59-165 FlowNet, :274-347 FFWM) are plain
-``nn.Conv2d`` layers; their forward and data gradient stay with the vendor library (Winograd fp32, ~100
-TFLOP/s effective on MI355X), but the weight gradient of the large-image 3x3 layers -- above all dres2's
-195 -> 195 channels at 128 x 128, 1.7 ms per call in the vendor library -- is computed by
-``ffwm_conv3x3_wgrad``.  ``route_conv_wgrad(net)`` re-classes the eligible layers in place, so parameter
-names, state dicts and spectral-norm hooks are untouched.
+The conv stacks of the reference (models/base_networks.py:59-165 FlowNet, :274-347 FFWM) are plain ``nn.Conv2d`` /
+``nn.ConvTranspose2d`` layers.  Each ``route_*`` function re-classes the eligible layers of a network in place, so parameter
+names, state dicts and spectral-norm hooks are untouched; ``route_training_kernels(net)`` applies them in the trainer's order:
+
+* ``route_conv_wgrad``: the weight gradient of the 3x3 / stride 1 layers on ``ffwm_conv3x3_wgrad`` (csrc/conv_wgrad.hip, and its
+  Winograd-domain kernel csrc/conv_wgrad_wino.hip) -- above all dres2's 195 -> 195 channels at 128 x 128;
+* ``route_conv_winograd``: forward and data gradient of the same layers on the Winograd F(2x2, 3x3) kernel
+  (csrc/conv_winograd.hip) where the plane is large enough (``winograd_dirs``, which asks ``ffwm_conv3x3_winograd_splits`` how the
+  library would cut the call), else the vendor library;
+* ``route_conv_fwd``: forward of the 3x3 / 4x4, stride 1 / 2 convolutions and forward + data gradient of
+  ConvTranspose2d(4, 2, 1) on csrc/conv_fwd.hip;
+* ``route_conv_bwd``: the weight gradient of every remaining convolution the tiled kernel serves (csrc/conv_bwd.hip);
+* ``route_flow_heads``: FlowNet's flow heads and 2 -> 2 upsamplers on the direct kernels of csrc/flownet_ops.hip.
+
+A direction no kernel here serves stays with the vendor library through ATen; the FFWM_* environment switches below are read once,
+at import.
 """
+import os as _os
+
 import torch
 import torch.nn as nn
 from torch.autograd import Function
 
 from . import ops
 
-
-import os as _os0
-_WGRAD_W64 = _os0.environ.get("FFWM_WGRAD_W64", "1") == "1"      # round 6: on -- the 64-pixel layers with aligned channel counts (att convs of the 64 x 64 level) reach the Winograd-domain kernel: warp + attention sub-path 1902 -> 1940 img/s, train step unchanged
+_WGRAD_W64 = _os.environ.get("FFWM_WGRAD_W64", "1") == "1"      # round 6: on -- the 64-pixel layers with aligned channel counts (att convs of the 64 x 64 level) reach the Winograd-domain kernel: warp + attention sub-path 1902 -> 1940 img/s, train step unchanged
 
 
 class _Conv3x3MfmaWgrad(Function):
@@ -105,9 +115,8 @@ def route_conv_wgrad(net):
 #     FlowNet's 2 x 2 ... 8 x 8 tail and on the thin heads, level on the 256-384 channel layers at 32 x 32), one launch + at most
 #     one memset instead of five to eight launches, and the bias gradient comes out of the same pass;
 #   * left with the vendor: image heads (<= 4 output channels) on large planes, where a 64-row MFMA tile is mostly empty.
-import os as _os1
-_TILED_WGRAD = _os1.environ.get("FFWM_TILED_WGRAD", "1") != "0"
-_TILED_WGRAD_1X1 = _os1.environ.get("FFWM_TILED_WGRAD_1X1", "1") != "0"
+_TILED_WGRAD = _os.environ.get("FFWM_TILED_WGRAD", "1") != "0"
+_TILED_WGRAD_1X1 = _os.environ.get("FFWM_TILED_WGRAD_1X1", "1") != "0"
 
 
 def _tiled_wgrad_wins(rows, gathered, kernel):
@@ -208,7 +217,6 @@ def conv_transpose_weight_grad(x, go, weight, need_b):
 # MFMA units: 1.5-1.9 x the vendor's VALU Winograd on the layers that dominate the train step (netG's 195 -> 195 residual
 # blocks at 128^2 / 64^2: 0.62 ms against 0.93 ms; 256 channels at 128^2: 0.71 against 1.32 ms).  Small planes stay with the
 # vendor: below ~2000 tiles the 64 x 64-tile workgroups do not fill the chip.
-import os as _os
 _WINOGRAD = _os.environ.get("FFWM_WINOGRAD", "1") != "0"
 WINOGRAD_MIN_TILES = int(_os.environ.get("FFWM_WINOGRAD_MIN_TILES", 2048))
 # (strips of 64 tiles) x (tiles of 64 output channels) a call must offer the 256 persistent workgroups: measured per shape of

@@ -99,18 +99,13 @@ int launch(const T* flow, const T* M, T* loss, T* gflow, int64_t B, int64_t h, i
     // (b, grid) plane set = 1 / (B h' w')), and the gradient of that w.r.t. flow is 2 r * 64 * loss_scale
     const T gscale = static_cast<T>(2.0 * 64.0 * loss_scale);
     LaunchScope ls("affine_regularization", st, sizeof(T) * static_cast<double>(B) * 2 * h * w * (gflow ? 2.0 : 1.0));
-#define FFWM_AR(KK)                                                                                          \
-    case KK:                                                                                                 \
-        hipLaunchKernelGGL((affine_reg_kernel<T, KK>), dim3(grid), dim3(kBlock), 0, st, flow, M, loss, gflow, \
-                           (int)h, (int)w, tiles_x, tiles_y, gscale);                                        \
-        break;
-    switch (kz) {
-        FFWM_AR(3) FFWM_AR(5) FFWM_AR(7)
-        default:
-            set_error("ffwm_affine_regularization: kernel size %d is not built (3, 5, 7: the sizes the reference uses)", kz);
-            return FFWM_ERR_ARG;
+    if (!dispatch<3, 5, 7>(kz, [&](auto KK) {
+            hipLaunchKernelGGL((affine_reg_kernel<T, KK.value>), dim3(grid), dim3(kBlock), 0, st, flow, M, loss, gflow, (int)h, (int)w, tiles_x,
+                               tiles_y, gscale);
+        })) {
+        set_error("ffwm_affine_regularization: kernel size %d is not built (3, 5, 7: the sizes the reference uses)", kz);
+        return FFWM_ERR_ARG;
     }
-#undef FFWM_AR
     return check_launch("ffwm_affine_regularization");
 }
 

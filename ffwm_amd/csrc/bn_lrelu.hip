@@ -377,6 +377,21 @@ static int bn_slices(int64_t B, int64_t C, int64_t HW, const void* scratch) {
     return S < 2 ? 1 : static_cast<int>(S);
 }
 
+// The route of one call, for the four entry points: a channel cut into S slices in two phases (scratch given), else one 1024-thread
+// workgroup per channel, else (fewer than 2048 values per channel) a wave per channel, 16 channels to a workgroup.
+// kernel(THR, grid, g) launches the entry point's kernel<THR.value, ...> with its own pointers.
+template <class F>
+static int bn_launch(const char* fn, BnGeo g, const void* scratch, F&& kernel) {
+    const int64_t B = g.B, C = g.C, HW = g.HW;
+    g.S = bn_slices(B, C, HW, scratch);          // (> 1 only from 2048 values per channel up)
+    const int threads = B * HW >= 2048 ? kBnThreads : kWave, per_block = kBnThreads / threads;
+    const dim3 grid(static_cast<unsigned>((C + per_block - 1) / per_block), static_cast<unsigned>(g.S));
+    const bool ok = dispatch<kBnThreads, kWave>(threads, [&](auto THR) {
+        for (g.phase = g.S > 1 ? 1 : 0; g.phase <= (g.S > 1 ? 2 : 0); ++g.phase) kernel(THR, grid, g);
+    });
+    return ok ? check_launch(fn) : no_kernel(fn);
+}
+
 extern "C" int ffwm_bn_lrelu_forward(const void* x, const void* weight, const void* bias, void* running_mean,
                                      void* running_var, void* y, void* save_mean, void* save_invstd, void* scratch, int64_t B,
                                      int64_t C, int64_t HW, double eps, double momentum, double negative_slope, int dtype,
@@ -385,27 +400,14 @@ extern "C" int ffwm_bn_lrelu_forward(const void* x, const void* weight, const vo
     if (int rc = check_bn(fn, B, C, HW, dtype)) return rc;
     FFWM_REQUIRE(x && y && save_mean && save_invstd, FFWM_ERR_ARG, "%s: NULL tensor pointer", fn);
     FFWM_REQUIRE((running_mean == nullptr) == (running_var == nullptr), FFWM_ERR_ARG, "%s: running_mean and running_var go together", fn);
-    BnGeo g{(int)B, (int)C, (int)HW, (float)eps, (float)momentum, (float)negative_slope, 1, 0};
     hipStream_t st = static_cast<hipStream_t>(stream);
     LaunchScope ls("bn_lrelu_fwd", st, 4.0 * 2.0 * B * C * HW);
-#define FFWM_BN_FWD(THR, GRID)                                                                                              \
-    hipLaunchKernelGGL((bn_lrelu_fwd_kernel<THR>), GRID, dim3(kBnThreads), 0, st, (const float*)x, (const float*)weight,    \
-                       (const float*)bias, (float*)running_mean, (float*)running_var, (float*)y, (float*)save_mean,         \
-                       (float*)save_invstd, g, (double*)scratch)
-    const int S = bn_slices(B, C, HW, scratch);
-    if (S > 1) {
-        g.S = S;
-        g.phase = 1;
-        FFWM_BN_FWD(kBnThreads, dim3((unsigned)C, (unsigned)S));
-        g.phase = 2;
-        FFWM_BN_FWD(kBnThreads, dim3((unsigned)C, (unsigned)S));
-    } else if (B * HW >= 2048) {
-        FFWM_BN_FWD(kBnThreads, dim3((unsigned)C));
-    } else {
-        FFWM_BN_FWD(kWave, dim3((unsigned)((C + 15) / 16)));
-    }
-#undef FFWM_BN_FWD
-    return check_launch(fn);
+    return bn_launch(fn, BnGeo{(int)B, (int)C, (int)HW, (float)eps, (float)momentum, (float)negative_slope, 1, 0}, scratch,
+                     [&](auto THR, dim3 grid, const BnGeo& g) {
+                         hipLaunchKernelGGL((bn_lrelu_fwd_kernel<THR.value>), grid, dim3(kBnThreads), 0, st, (const float*)x, (const float*)weight,
+                                            (const float*)bias, (float*)running_mean, (float*)running_var, (float*)y, (float*)save_mean,
+                                            (float*)save_invstd, g, (double*)scratch);
+                     });
 }
 
 extern "C" int ffwm_bn_lrelu_backward(const void* x, const void* grad_out, const void* weight, const void* bias,
@@ -415,27 +417,14 @@ extern "C" int ffwm_bn_lrelu_backward(const void* x, const void* grad_out, const
     const char* fn = "ffwm_bn_lrelu_backward";
     if (int rc = check_bn(fn, B, C, HW, dtype)) return rc;
     FFWM_REQUIRE(x && grad_out && save_mean && save_invstd, FFWM_ERR_ARG, "%s: NULL tensor pointer", fn);
-    BnGeo g{(int)B, (int)C, (int)HW, 0.f, 0.f, (float)negative_slope, 1, 0};
     hipStream_t st = static_cast<hipStream_t>(stream);
     LaunchScope ls("bn_lrelu_bwd", st, 4.0 * 3.0 * B * C * HW);
-#define FFWM_BN_BWD(THR, GRID)                                                                                              \
-    hipLaunchKernelGGL((bn_lrelu_bwd_kernel<THR>), GRID, dim3(kBnThreads), 0, st, (const float*)x, (const float*)grad_out,  \
-                       (const float*)weight, (const float*)bias, (const float*)save_mean, (const float*)save_invstd,        \
-                       (float*)grad_x, (float*)grad_weight, (float*)grad_bias, g, (double*)scratch)
-    const int S = bn_slices(B, C, HW, scratch);
-    if (S > 1) {
-        g.S = S;
-        g.phase = 1;
-        FFWM_BN_BWD(kBnThreads, dim3((unsigned)C, (unsigned)S));
-        g.phase = 2;
-        FFWM_BN_BWD(kBnThreads, dim3((unsigned)C, (unsigned)S));
-    } else if (B * HW >= 2048) {
-        FFWM_BN_BWD(kBnThreads, dim3((unsigned)C));
-    } else {
-        FFWM_BN_BWD(kWave, dim3((unsigned)((C + 15) / 16)));
-    }
-#undef FFWM_BN_BWD
-    return check_launch(fn);
+    return bn_launch(fn, BnGeo{(int)B, (int)C, (int)HW, 0.f, 0.f, (float)negative_slope, 1, 0}, scratch,
+                     [&](auto THR, dim3 grid, const BnGeo& g) {
+                         hipLaunchKernelGGL((bn_lrelu_bwd_kernel<THR.value>), grid, dim3(kBnThreads), 0, st, (const float*)x, (const float*)grad_out,
+                                            (const float*)weight, (const float*)bias, (const float*)save_mean, (const float*)save_invstd,
+                                            (float*)grad_x, (float*)grad_weight, (float*)grad_bias, g, (double*)scratch);
+                     });
 }
 
 // ---- the tail of a residual block: y = act(BatchNorm(x) + res + rbias[c]) (base_networks.py:207-233: activ(blocks(x) + input(x)) with
@@ -449,27 +438,14 @@ extern "C" int ffwm_bn_res_act_forward(const void* x, const void* weight, const 
     FFWM_REQUIRE(x && y && res && save_mean && save_invstd, FFWM_ERR_ARG, "%s: NULL tensor pointer", fn);
     FFWM_REQUIRE(act == 0 || act == 1, FFWM_ERR_ARG, "%s: act must be 0 (leaky relu) or 1 (sigmoid)", fn);
     FFWM_REQUIRE((running_mean == nullptr) == (running_var == nullptr), FFWM_ERR_ARG, "%s: running_mean and running_var go together", fn);
-    BnGeo g{(int)B, (int)C, (int)HW, (float)eps, (float)momentum, (float)negative_slope, 1, 0, act};
     hipStream_t st = static_cast<hipStream_t>(stream);
     LaunchScope ls("bn_res_act_fwd", st, 4.0 * 3.0 * B * C * HW);
-#define FFWM_BNR_FWD(THR, GRID)                                                                                                  \
-    hipLaunchKernelGGL((bn_lrelu_fwd_kernel<THR, true>), GRID, dim3(kBnThreads), 0, st, (const float*)x, (const float*)weight,     \
-                       (const float*)bias, (float*)running_mean, (float*)running_var, (float*)y, (float*)save_mean,               \
-                       (float*)save_invstd, g, (double*)scratch, (const float*)res, (const float*)rbias)
-    const int S = bn_slices(B, C, HW, scratch);
-    if (S > 1) {
-        g.S = S;
-        g.phase = 1;
-        FFWM_BNR_FWD(kBnThreads, dim3((unsigned)C, (unsigned)S));
-        g.phase = 2;
-        FFWM_BNR_FWD(kBnThreads, dim3((unsigned)C, (unsigned)S));
-    } else if (B * HW >= 2048) {
-        FFWM_BNR_FWD(kBnThreads, dim3((unsigned)C));
-    } else {
-        FFWM_BNR_FWD(kWave, dim3((unsigned)((C + 15) / 16)));
-    }
-#undef FFWM_BNR_FWD
-    return check_launch(fn);
+    return bn_launch(fn, BnGeo{(int)B, (int)C, (int)HW, (float)eps, (float)momentum, (float)negative_slope, 1, 0, act}, scratch,
+                     [&](auto THR, dim3 grid, const BnGeo& g) {
+                         hipLaunchKernelGGL((bn_lrelu_fwd_kernel<THR.value, true>), grid, dim3(kBnThreads), 0, st, (const float*)x, (const float*)weight,
+                                            (const float*)bias, (float*)running_mean, (float*)running_var, (float*)y, (float*)save_mean,
+                                            (float*)save_invstd, g, (double*)scratch, (const float*)res, (const float*)rbias);
+                     });
 }
 
 // grad_res = grad_out * act'(.) (from the saved output y), grad_x = the BatchNorm backward of it, grad_weight / grad_bias the
@@ -482,25 +458,12 @@ extern "C" int ffwm_bn_res_act_backward(const void* x, const void* y, const void
     if (int rc = check_bn(fn, B, C, HW, dtype)) return rc;
     FFWM_REQUIRE(x && y && grad_out && save_mean && save_invstd, FFWM_ERR_ARG, "%s: NULL tensor pointer", fn);
     FFWM_REQUIRE(act == 0 || act == 1, FFWM_ERR_ARG, "%s: act must be 0 (leaky relu) or 1 (sigmoid)", fn);
-    BnGeo g{(int)B, (int)C, (int)HW, 0.f, 0.f, (float)negative_slope, 1, 0, act};
     hipStream_t st = static_cast<hipStream_t>(stream);
     LaunchScope ls("bn_res_act_bwd", st, 4.0 * 5.0 * B * C * HW);
-#define FFWM_BNR_BWD(THR, GRID)                                                                                                  \
-    hipLaunchKernelGGL((bn_lrelu_bwd_kernel<THR, true>), GRID, dim3(kBnThreads), 0, st, (const float*)x, (const float*)grad_out,   \
-                       (const float*)weight, (const float*)nullptr, (const float*)save_mean, (const float*)save_invstd,           \
-                       (float*)grad_x, (float*)grad_weight, (float*)grad_bias, g, (double*)scratch, (const float*)y, (float*)grad_res)
-    const int S = bn_slices(B, C, HW, scratch);
-    if (S > 1) {
-        g.S = S;
-        g.phase = 1;
-        FFWM_BNR_BWD(kBnThreads, dim3((unsigned)C, (unsigned)S));
-        g.phase = 2;
-        FFWM_BNR_BWD(kBnThreads, dim3((unsigned)C, (unsigned)S));
-    } else if (B * HW >= 2048) {
-        FFWM_BNR_BWD(kBnThreads, dim3((unsigned)C));
-    } else {
-        FFWM_BNR_BWD(kWave, dim3((unsigned)((C + 15) / 16)));
-    }
-#undef FFWM_BNR_BWD
-    return check_launch(fn);
+    return bn_launch(fn, BnGeo{(int)B, (int)C, (int)HW, 0.f, 0.f, (float)negative_slope, 1, 0, act}, scratch,
+                     [&](auto THR, dim3 grid, const BnGeo& g) {
+                         hipLaunchKernelGGL((bn_lrelu_bwd_kernel<THR.value, true>), grid, dim3(kBnThreads), 0, st, (const float*)x, (const float*)grad_out,
+                                            (const float*)weight, (const float*)nullptr, (const float*)save_mean, (const float*)save_invstd,
+                                            (float*)grad_x, (float*)grad_weight, (float*)grad_bias, g, (double*)scratch, (const float*)y, (float*)grad_res);
+                     });
 }

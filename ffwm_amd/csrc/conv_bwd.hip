@@ -420,10 +420,48 @@ extern "C" int ffwm_conv2d_wgrad(const void* rows, const void* gathered, void* g
     const float* a = static_cast<const float*>(rows);
     const float* x = static_cast<const float*>(gathered);
     float* dw = static_cast<float*>(grad_weight);
-    if (kernel == 3) hipLaunchKernelGGL((conv_wgrad_generic_kernel<3, 3>), grid, dim3(kBlock), 0, st, a, x, dw, g);
-    else if (kernel == 4) hipLaunchKernelGGL((conv_wgrad_generic_kernel<4, 4>), grid, dim3(kBlock), 0, st, a, x, dw, g);
-    else hipLaunchKernelGGL((conv_wgrad_generic_kernel<1, 1>), grid, dim3(kBlock), 0, st, a, x, dw, g);      // 1x1: the entry accepts it; it used to decode its columns as 4x4 taps
-    return check_launch(fn);
+    const bool ok = dispatch<1, 3, 4>(kernel, [&](auto R) {      // (1x1: the entry accepts it; it used to decode its columns as 4x4 taps)
+        hipLaunchKernelGGL((conv_wgrad_generic_kernel<R.value, R.value>), grid, dim3(kBlock), 0, st, a, x, dw, g);
+    });
+    return ok ? check_launch(fn) : no_kernel(fn);
+}
+
+// Tile shape (64 or 128 rows x 64 or 128 columns of dW) and pixel slices of the tiled weight gradient: the candidate with the
+// smallest estimated time, in units of one 32 x 32 x 32-pixel MFMA block per wave (1024 cycles).  A workgroup pays ~6 units of
+// prologue / epilogue, a sliced launch pays the atomic flush of its tile, and two workgroups per CU are resident (512 per round): a
+// launch of 567 workgroups runs as long as one of 1024, and FlowNet's 8 x 8 layers (16 chunks in all) are better off with 288
+// unsliced 64 x 128 tiles than with 432 slices of three 128 x 128 chunks each.
+struct Wg2Plan {
+    int wmt = 1, wnt = 1;        // 64-row / 64-column blocks of dW per workgroup tile
+    int k_tiles, n_tiles;
+    int64_t slices;
+};
+static Wg2Plan wg2_plan(int K, int N, int chunks_total) {
+    const int64_t wg_target = options().conv_wgrad_slice_target > 0 ? options().conv_wgrad_slice_target : 512;
+    // pixel slices of a launch of `tiles` workgroup tiles: up to the target, at least 4 chunks each
+    auto slices_for = [&](int64_t tiles) -> int64_t {
+        int64_t sl = tiles >= wg_target ? 1 : wg_target / tiles;
+        if (sl > chunks_total / 4) sl = chunks_total / 4;
+        return sl < 1 ? 1 : sl;
+    };
+    auto tiles_of = [](int n, int c) { return (n + 64 * c - 1) / (64 * c); };
+    Wg2Plan p;
+    double best = 1e30;
+    for (int cm = 1; cm <= 2; ++cm)
+        for (int cn = 1; cn <= 2; ++cn) {
+            if ((cm == 2 && K <= 64) || (cn == 2 && N <= 64)) continue;
+            const int64_t t = static_cast<int64_t>(tiles_of(K, cm)) * tiles_of(N, cn);
+            const int64_t sl = slices_for(t);
+            const int64_t per = (chunks_total + sl - 1) / sl;
+            const int64_t nzc = (chunks_total + per - 1) / per;
+            const int64_t rounds = (t * nzc + 511) / 512;
+            const double est = rounds * (per * cm * cn * (cm * cn == 1 ? 1.6 : (cm * cn == 2 ? 1.25 : 1.0)) + 6.0 + (nzc > 1 ? 2.0 * cm * cn : 0.0));
+            if (est < best) { best = est; p.wmt = cm; p.wnt = cn; }
+        }
+    p.k_tiles = tiles_of(K, p.wmt);
+    p.n_tiles = tiles_of(N, p.wnt);
+    p.slices = options().conv_wgrad_unsliced ? 1 : slices_for(static_cast<int64_t>(p.k_tiles) * p.n_tiles);
+    return p;
 }
 
 // Tiled variant: grad_weight (and grad_bias, when given: Conv2d only -- the row sums of `rows`) are OVERWRITTEN; the
@@ -457,33 +495,8 @@ extern "C" int ffwm_conv2d_wgrad_tiled(const void* rows, const void* gathered, v
     g.x_bytes = static_cast<unsigned>(B * C * H * W * 4);
     g.divP = make_fast_div(static_cast<unsigned>(g.P));
     g.divWo = make_fast_div(static_cast<unsigned>(g.Wo));
-    // tile shape (64 or 128 rows x 64 or 128 columns of dW) and pixel slices: the candidate with the smallest estimated time, in
-    // units of one 32 x 32 x 32-pixel MFMA block per wave (1024 cycles).  A workgroup pays ~6 units of prologue / epilogue, a
-    // sliced launch pays the atomic flush of its tile, and two workgroups per CU are resident (512 per round): a launch of 567
-    // workgroups runs as long as one of 1024, and FlowNet's 8 x 8 layers (16 chunks in all) are better off with 288 unsliced
-    // 64 x 128 tiles than with 432 slices of three 128 x 128 chunks each.
-    const int64_t wg_target = options().conv_wgrad_slice_target > 0 ? options().conv_wgrad_slice_target : 512;
-    int wmt = 1, wnt = 1;
-    double best = 1e30;
-    for (int cm = 1; cm <= 2; ++cm)
-        for (int cn = 1; cn <= 2; ++cn) {
-            if ((cm == 2 && g.K <= 64) || (cn == 2 && g.N <= 64)) continue;
-            const int64_t t = static_cast<int64_t>((g.K + 64 * cm - 1) / (64 * cm)) * ((g.N + 64 * cn - 1) / (64 * cn));
-            int64_t sl = t >= wg_target ? 1 : wg_target / t;
-            if (sl > g.chunks_total / 4) sl = g.chunks_total / 4;
-            if (sl < 1) sl = 1;
-            const int64_t per = (g.chunks_total + sl - 1) / sl;
-            const int64_t nzc = (g.chunks_total + per - 1) / per;
-            const int64_t rounds = (t * nzc + 511) / 512;
-            const double est = rounds * (per * cm * cn * (cm * cn == 1 ? 1.6 : (cm * cn == 2 ? 1.25 : 1.0)) + 6.0 + (nzc > 1 ? 2.0 * cm * cn : 0.0));
-            if (est < best) { best = est; wmt = cm; wnt = cn; }
-        }
-    const int k_tiles = (g.K + 64 * wmt - 1) / (64 * wmt), n_tiles = (g.N + 64 * wnt - 1) / (64 * wnt);
-    const int64_t tiles = static_cast<int64_t>(k_tiles) * n_tiles;
-    int64_t slices = tiles >= wg_target ? 1 : wg_target / tiles;
-    if (slices > g.chunks_total / 4) slices = g.chunks_total / 4;
-    if (slices < 1 || options().conv_wgrad_unsliced) slices = 1;
-    g.chunks = static_cast<int>((g.chunks_total + slices - 1) / slices);
+    const Wg2Plan p = wg2_plan(g.K, g.N, g.chunks_total);
+    g.chunks = static_cast<int>((g.chunks_total + p.slices - 1) / p.slices);
     g.nz = (g.chunks_total + g.chunks - 1) / g.chunks;
     hipStream_t st = static_cast<hipStream_t>(stream);
     float* dw = static_cast<float*>(grad_weight);
@@ -497,27 +510,18 @@ extern "C" int ffwm_conv2d_wgrad_tiled(const void* rows, const void* gathered, v
     const double flops = 2.0 * B * g.P * static_cast<double>(g.K) * g.N;
     const double bytes = 4.0 * (static_cast<double>(B) * K * g.P + static_cast<double>(B) * C * H * W + static_cast<double>(K) * g.N);
     LaunchScope ls("conv_wgrad_mfma_tiled", st, bytes, flops);
-    const dim3 grid(static_cast<unsigned>(n_tiles), static_cast<unsigned>(k_tiles), static_cast<unsigned>(g.nz));
+    const dim3 grid(static_cast<unsigned>(p.n_tiles), static_cast<unsigned>(p.k_tiles), static_cast<unsigned>(g.nz));
     const float* a = static_cast<const float*>(rows);
     const float* x = static_cast<const float*>(gathered);
-#define FFWM_WG2(RR, MM, NN)                                                                                                  \
-    do {                                                                                                                      \
-        auto kfn = conv_wgrad_tile_kernel<RR, RR, MM, NN>;                                                                    \
-        const size_t lds = 2u * (64 * MM + 64 * NN) * kW2P * sizeof(float);                                                   \
-        allow_large_lds(reinterpret_cast<const void*>(kfn));                                                                  \
-        hipLaunchKernelGGL(kfn, grid, dim3(kBlock), lds, st, a, x, dw, gb, g);                                                \
-    } while (0)
-#define FFWM_WG2_K(RR)                                                                                                        \
-    do {                                                                                                                      \
-        if (wmt == 2 && wnt == 2) FFWM_WG2(RR, 2, 2);                                                                         \
-        else if (wmt == 2) FFWM_WG2(RR, 2, 1);                                                                                \
-        else if (wnt == 2) FFWM_WG2(RR, 1, 2);                                                                                \
-        else FFWM_WG2(RR, 1, 1);                                                                                              \
-    } while (0)
-    if (kernel == 3) FFWM_WG2_K(3);
-    else if (kernel == 4) FFWM_WG2_K(4);
-    else FFWM_WG2_K(1);          // 1x1 (the shortcut convolution of netG's residual blocks, base_networks.py:213): a plain [K x P] . [P x C] product
-#undef FFWM_WG2_K
-#undef FFWM_WG2
-    return check_launch(fn);
+    const bool ok = dispatch<1, 3, 4>(kernel, [&](auto R) {      // (1 x 1: the shortcut convolution of netG's residual blocks, base_networks.py:213 -- a plain [K x P] . [P x C] product)
+        return dispatch<1, 2>(p.wmt, [&](auto MM) {
+            return dispatch<1, 2>(p.wnt, [&](auto NN) {
+                auto kfn = conv_wgrad_tile_kernel<R.value, R.value, MM.value, NN.value>;
+                const size_t lds = 2u * (64 * MM.value + 64 * NN.value) * kW2P * sizeof(float);
+                allow_large_lds(reinterpret_cast<const void*>(kfn));
+                hipLaunchKernelGGL(kfn, grid, dim3(kBlock), lds, st, a, x, dw, gb, g);
+            });
+        });
+    });
+    return ok ? check_launch(fn) : no_kernel(fn);
 }

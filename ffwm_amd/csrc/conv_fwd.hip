@@ -452,7 +452,7 @@ extern "C" int ffwm_conv2d_forward(const void* input, const void* weight, const 
         if (rc != FFWM_OK) return rc;
     }
     ConvGeo& g = pl.g;
-    const int mode = pl.mode, tm = pl.tm, tn = pl.tn, classes = pl.classes;
+    const int mode = pl.mode, classes = pl.classes;
     const int64_t oplane = static_cast<int64_t>(g.oH) * g.oW;
     FFWM_REQUIRE(out_batch_stride >= K * oplane, FFWM_ERR_ARG, "%s: output batch stride smaller than K * Ho * Wo", fn);
     FFWM_REQUIRE(!output2 || out2_batch_stride >= K * oplane, FFWM_ERR_ARG, "%s: second output's batch stride smaller than K * Ho * Wo", fn);
@@ -473,19 +473,18 @@ extern "C" int ffwm_conv2d_forward(const void* input, const void* weight, const 
     float* o2 = split ? nullptr : static_cast<float*>(output2);
     {
         LaunchScope ls(kScope[mode], st, bytes, flops);
-#define FFWM_CONV_LAUNCH(M, RR, SS)                                                                                          \
-    do {                                                                                                                   \
-        if (tm == 128 && tn == 128) hipLaunchKernelGGL((conv_fwd_kernel<M, RR, SS, 128, 128>), grid, dim3(kBlock), 0, st, x, wt, bs, o, o2, g); \
-        else if (tm == 128) hipLaunchKernelGGL((conv_fwd_kernel<M, RR, SS, 128, 64>), grid, dim3(kBlock), 0, st, x, wt, bs, o, o2, g);          \
-        else if (tn == 128) hipLaunchKernelGGL((conv_fwd_kernel<M, RR, SS, 64, 128>), grid, dim3(kBlock), 0, st, x, wt, bs, o, o2, g);          \
-        else hipLaunchKernelGGL((conv_fwd_kernel<M, RR, SS, 64, 64>), grid, dim3(kBlock), 0, st, x, wt, bs, o, o2, g);                          \
-    } while (0)
-        if (mode == 1) FFWM_CONV_LAUNCH(1, 2, 2);
-        else if (mode == 2) FFWM_CONV_LAUNCH(2, 2, 2);
-        else if (mode == 3) FFWM_CONV_LAUNCH(3, 3, 3);
-        else if (pl.kernel == 3) FFWM_CONV_LAUNCH(0, 3, 3);
-        else FFWM_CONV_LAUNCH(0, 4, 4);
-#undef FFWM_CONV_LAUNCH
+        // kernel<MODE, R, S, TM, TN>: the stride-2 operators of modes 1 / 2 walk 2 x 2 taps per parity class, the others the layer's own
+        // 3 x 3 or 4 x 4 (conv_plan has checked mode and kernel) -- one key, 10 MODE + R, so that only these five are instantiated
+        const int taps = (mode == 1 || mode == 2) ? 2 : pl.kernel;
+        const bool ok = dispatch<12, 22, 33, 3, 4>(10 * mode + taps, [&](auto MR) {
+            return dispatch<64, 128>(pl.tm, [&](auto TM) {
+                return dispatch<64, 128>(pl.tn, [&](auto TN) {
+                    hipLaunchKernelGGL((conv_fwd_kernel<MR.value / 10, MR.value % 10, MR.value % 10, TM.value, TN.value>), grid, dim3(kBlock), 0, st,
+                                       x, wt, bs, o, o2, g);
+                });
+            });
+        });
+        if (!ok) return no_kernel(fn);
         rc = check_launch(fn);
         if (rc != FFWM_OK) return rc;
     }
@@ -497,11 +496,9 @@ extern "C" int ffwm_conv2d_forward(const void* input, const void* weight, const 
                      (!y2 || (reinterpret_cast<uintptr_t>(y2) % 16 == 0 && out2_batch_stride % 4 == 0));
     const int64_t total = pl.out_elems / (vec ? 4 : 1);
     LaunchScope ls("conv_fwd_split_reduce", st, 4.0 * pl.out_elems * (g.splitk + 1.0 + (y2 ? 1 : 0)));
-    if (vec)
-        hipLaunchKernelGGL((conv_split_reduce_kernel<4>), dim3(ew_grid(total)), dim3(kBlock), 0, st, static_cast<const float*>(workspace), bs, y, y2,
+    dispatch<4, 1>(vec ? 4 : 1, [&](auto VEC) {
+        hipLaunchKernelGGL((conv_split_reduce_kernel<VEC.value>), dim3(ew_grid(total)), dim3(kBlock), 0, st, static_cast<const float*>(workspace), bs, y, y2,
                            total, g.splitk, pl.out_elems, static_cast<int>(K), static_cast<int>(oplane), out_batch_stride, out2_batch_stride, act, g.slope);
-    else
-        hipLaunchKernelGGL((conv_split_reduce_kernel<1>), dim3(ew_grid(total)), dim3(kBlock), 0, st, static_cast<const float*>(workspace), bs, y, y2,
-                           total, g.splitk, pl.out_elems, static_cast<int>(K), static_cast<int>(oplane), out_batch_stride, out2_batch_stride, act, g.slope);
+    });
     return check_launch(fn);
 }

@@ -391,11 +391,8 @@ extern "C" int ffwm_conv3x3_wgrad_block(const void* input, const void* grad_outp
     // the full tiles on the Winograd-domain kernel (conv_wgrad_wino.hip; it sums its dY rows on the way like the direct kernel) when it
     // serves the shape and -- conv_wgrad_wino 0 = auto -- every CU gets >= 16 chunks of it (1 = whenever served, 2 = never); a shape
     // it leaves comes back > 0 and takes the direct kernel
-    int wino = 1;
-    if (options().conv_wgrad_wino != 2 && km > k_begin && cm > c_begin) {
-        wino = launch_wgrad_wino(X, G, dW, main_has_bias ? db : nullptr, B, C, K, H, W, k_begin, km, c_begin, cm, st);
-        if (wino < 0) return wino;
-    }
+    const int wino = launch_wgrad_wino(X, G, dW, main_has_bias ? db : nullptr, B, C, K, H, W, k_begin, km, c_begin, cm, st);
+    if (wino < 0) return wino;
     if (wino != FFWM_OK)
         if (int rc = launch_wgrad<false>("conv3x3_wgrad", X, G, dW, B, C, K, H, W, k_begin, km, c_begin, cm, C * 9, 9, 0, st,
                                          main_has_bias ? db : nullptr))

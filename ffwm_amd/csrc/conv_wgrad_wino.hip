@@ -301,11 +301,12 @@ conv3x3_wgrad_wino_kernel(const float* __restrict__ X, const float* __restrict__
 
 // The main (full 64-channel tiles) part of ffwm_conv3x3_wgrad_block on the Winograd-domain kernel: grad_weight[k_begin:k_end,
 // c_begin:c_end] += ...  (the caller zero-filled grad_weight).  Returns FFWM_OK after the launch, or a positive value when the
-// shape is not served (odd sizes, W not a multiple of 16, too few chunks): the caller then uses the direct kernel.
+// shape is not served (odd sizes, W not a multiple of 16, too few chunks) or option conv_wgrad_wino says 2 = never: the caller then
+// uses the direct kernel.  An empty block is FFWM_OK with nothing launched, as it is for the direct kernel.
 int launch_wgrad_wino(const float* X, const float* G, float* dW, float* dbias, int64_t B, int64_t C, int64_t K, int64_t H, int64_t W,
                       int64_t k_begin, int64_t k_end, int64_t c_begin, int64_t c_end, hipStream_t st) {
     if (k_begin >= k_end || c_begin >= c_end) return FFWM_OK;
-    if ((H & 1) || (W & 15) || B * C * H * W * 4 >= (1LL << 32) - 64 || B * K * H * W * 4 >= (1LL << 32) - 64) return 1;
+    if (options().conv_wgrad_wino == 2 || (H & 1) || (W & 15) || B * C * H * W * 4 >= (1LL << 32) - 64 || B * K * H * W * 4 >= (1LL << 32) - 64) return 1;
     WwGeo g;
     g.C = static_cast<int>(C); g.K = static_cast<int>(K); g.H = static_cast<int>(H); g.W = static_cast<int>(W);
     g.k_begin = static_cast<int>(k_begin); g.k_end = static_cast<int>(k_end);

@@ -1112,30 +1112,69 @@ using namespace ffwm;
 // profiles/r04_winograd_split.txt): with shorter splits the prologue / epilogue of a workgroup, the zero-fill and the atomics
 // cost more than the idle CUs (64 -> 64 at 64 x 64: 35 -> 50 us), with 16 chunks 256 -> 256 at 32 x 32 goes 106 -> 92 us and
 // 512 -> 512 at 16 x 16 199 -> 99 us.  Only without a fused activation (the epilogue of a split cannot apply one); 1 = no split.
-static int winograd_splits(int pairs, int CH, int act, int cus) {
+static int winograd_splits(int64_t pairs, int64_t CH, int act, int cus) {
     if (act != 0 || !options().conv_wino_split || pairs <= 0) return 1;
     for (int cs = options().conv_wino_split == 2 ? 2 : 4; cs >= 2; cs -= 2) {          // (2: capped -- a + b is order-independent, a + b + c + d is not)
         if (pairs * cs > cus) continue;
         if (CH % cs != 0) continue;
-        const int chs = CH / cs;
+        const int64_t chs = CH / cs;
         if (chs < 16 || (chs & 1)) continue;
         return cs;
     }
     return 1;
 }
 
+// The route of one call, decided once: the splits query, the weight transforms (per call and batched) and the launch all read this
+// plan, so they cannot disagree.  WinoChannels is the part that (K, C, W % 4 == 0) alone decide -- all that
+// ffwm_conv3x3_winograd_weights_multi knows of the later call.
+struct WinoChannels {
+    int tail;                // output channels past a multiple of 64 that the thin direct kernel computes (1-4), 0 = no thin launch
+    int64_t K, KT, CH;       // output channels of the MFMA kernel (a multiple of 64 under a thin tail, 0 when K <= 4), their 64-tiles, chunks of 8 input channels
+    int64_t elems;           // elements the weight transform computes, one per thread: the padded U, then the thin tail's weights
+};
+static WinoChannels wino_channels(int64_t K, int64_t C, bool width_multiple_of_4) {
+    WinoChannels c;
+    // a tail of 1-4 channels past a multiple of 64 goes to the thin kernel instead of costing a 64-channel tile
+    // (K <= 4 altogether -- netG's 195 -> 3 output layer, base_networks.py:312 -- is the thin kernel alone)
+    const int tail = static_cast<int>(K % 64);
+    c.tail = (K > 64 || K <= 4) && tail >= 1 && tail <= 4 && width_multiple_of_4 && options().conv_thin_tail ? tail : 0;
+    c.K = K - c.tail;
+    c.KT = (c.K + 63) / 64;
+    c.CH = (C + 7) / 8;
+    c.elems = c.KT * 64 * c.CH * 8 + (c.tail ? C * kThinStride : 0);
+    return c;
+}
+struct WinoPlan {
+    WinoChannels ch;
+    int64_t T, pairs;        // output tiles; (strip of 64 tiles, k tile) pairs = the workgroups of the generic kernel
+    bool raw;                // whole tile rows of one image per workgroup -> the raw-staged variants (g.R, g.ROWS)
+    int split_n;             // pieces the reduction of a raw-staged call is cut into (1 = whole)
+    WinoGeo g;               // all but slope, x_bytes, u_bytes; valid once the caller has checked that T fits an int
+};
+static WinoPlan wino_plan(int64_t B, int64_t C, int64_t H, int64_t W, int64_t K, int act, bool width_multiple_of_4) {
+    WinoPlan p;
+    p.ch = wino_channels(K, C, width_multiple_of_4);
+    const int64_t TH = (H + 1) / 2, TW = (W + 1) / 2;
+    p.T = B * TH * TW;
+    const int64_t TT = (p.T + kWinoTiles - 1) / kWinoTiles;
+    p.pairs = TT * p.ch.KT;
+    p.raw = options().conv_wino_raw && (W == 16 || W == 32 || W == 64 || W == 128) && H % 2 == 0 && TW <= 64 && 64 % TW == 0 &&
+            TH % (64 / TW) == 0 && (2 * (64 / TW) + 2) * W * 8 <= kWinoRawFloats;
+    p.split_n = p.raw ? winograd_splits(p.pairs, p.ch.CH, act, device_cus()) : 1;
+    WinoGeo& g = p.g;
+    g.C = static_cast<int>(C); g.H = static_cast<int>(H); g.W = static_cast<int>(W);
+    g.K = static_cast<int>(p.ch.K); g.Kout = static_cast<int>(K);
+    g.TH = static_cast<int>(TH); g.TW = static_cast<int>(TW); g.T = static_cast<int>(p.T);
+    g.CH = static_cast<int>(p.ch.CH); g.KT = static_cast<int>(p.ch.KT); g.TT = static_cast<int>(TT);
+    g.act = act;
+    g.R = p.raw ? 64 / g.TW : 0;
+    g.ROWS = 2 * g.R + 2;
+    return p;
+}
+
 extern "C" int ffwm_conv3x3_winograd_splits(int64_t B, int64_t C, int64_t H, int64_t W, int64_t K, int act) {
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || K <= 0) return 1;
-    const bool rawshape = options().conv_wino_raw && (W == 16 || W == 32 || W == 64 || W == 128) && H % 2 == 0;
-    if (!rawshape) return 1;
-    const int TH = static_cast<int>((H + 1) / 2), TW = static_cast<int>((W + 1) / 2);
-    if (!(TW <= 64 && 64 % TW == 0 && TH % (64 / TW) == 0)) return 1;
-    const int tail = static_cast<int>(K % 64);
-    const bool thin = (K > 64 || K <= 4) && tail >= 1 && tail <= 4 && W % 4 == 0 && options().conv_thin_tail;
-    const int64_t Kw = thin ? K - tail : K;
-    const int64_t pairs = ((B * TH * TW + kWinoTiles - 1) / kWinoTiles) * ((Kw + 63) / 64);
-    if (pairs <= 0 || pairs > 4096) return 1;
-    return winograd_splits(static_cast<int>(pairs), static_cast<int>((C + 7) / 8), act, device_cus());
+    return wino_plan(B, C, H, W, K, act, W % 4 == 0).split_n;
 }
 
 extern "C" int64_t ffwm_conv3x3_winograd_workspace_bytes(int64_t K, int64_t C) {
@@ -1167,23 +1206,20 @@ extern "C" int ffwm_conv3x3_winograd_weights_multi(const ffwm_wino_weights* item
         FFWM_REQUIRE(w.weight && w.workspace && w.K > 0 && w.C > 0 && (w.data_gradient == 0 || w.data_gradient == 1), FFWM_ERR_ARG,
                      "%s: item %d: NULL pointer, non-positive size or data_gradient not 0 / 1", fn, i);
         FFWM_REQUIRE(ffwm_conv3x3_winograd_workspace_bytes(w.K, w.C) < (1LL << 31), FFWM_ERR_SIZE, "%s: item %d: workspace beyond 2 GiB", fn, i);
-        // the same split of the output channels as ffwm_conv3x3_winograd_forward makes for this (K, W % 4)
-        const int tail = static_cast<int>(w.K % 64);
-        const bool thin = (w.K > 64 || w.K <= 4) && tail >= 1 && tail <= 4 && w.width_multiple_of_4 && options().conv_thin_tail;
+        const WinoChannels ch = wino_channels(w.K, w.C, w.width_multiple_of_4 != 0);
         WinoWeightsItem& q = tab.it[tab.n];
         q.w = static_cast<const float*>(w.weight);
         q.U = static_cast<float*>(w.workspace);
-        q.K = static_cast<int>(thin ? w.K - tail : w.K);
+        q.K = static_cast<int>(ch.K);
         q.Kw = static_cast<int>(w.K);
         q.C = static_cast<int>(w.C);
-        q.CH = (q.C + 7) / 8;
-        q.KT = (q.K + 63) / 64;
+        q.CH = static_cast<int>(ch.CH);
+        q.KT = static_cast<int>(ch.KT);
         q.mode = w.data_gradient;
-        q.tail = thin ? tail : 0;
+        q.tail = ch.tail;
         q.begin = blocks;
-        const int64_t elems = static_cast<int64_t>(q.KT) * 64 * q.CH * 8 + (thin ? w.C * kThinStride : 0);
-        blocks += static_cast<int>((elems + kBlock - 1) / kBlock);
-        bytes += 4.0 * (9.0 * w.K * w.C + 16.0 * elems);
+        blocks += static_cast<int>((ch.elems + kBlock - 1) / kBlock);
+        bytes += 4.0 * (9.0 * w.K * w.C + 16.0 * ch.elems);
         if (++tab.n == kWinoMaxMulti)
             if (int rc = flush()) return rc;
     }
@@ -1202,98 +1238,62 @@ extern "C" int ffwm_conv3x3_winograd_forward(const void* input, const void* weig
     const bool reuse = (data_gradient & 2) != 0;         // the workspace holds the transformed weights of an earlier, identical call
     data_gradient &= 1;
     FFWM_REQUIRE(B * C * H * W < (1LL << 29) && B * K * H * W < (1LL << 40), FFWM_ERR_SIZE, "%s: the input must stay below 2 GiB", fn);
-    // a tail of 1-4 channels past a multiple of 64 goes to the thin kernel instead of costing a 64-channel tile
-    const int tail = static_cast<int>(K % 64);
-    // (K <= 4 altogether -- netG's 195 -> 3 output layer, base_networks.py:312 -- is the thin kernel alone)
-    const bool thin = (K > 64 || K <= 4) && tail >= 1 && tail <= 4 && W % 4 == 0 && options().conv_thin_tail;
-    WinoGeo g;
-    g.C = static_cast<int>(C); g.H = static_cast<int>(H); g.W = static_cast<int>(W);
-    g.K = static_cast<int>(thin ? K - tail : K);
-    g.Kout = static_cast<int>(K);
-    g.TH = (g.H + 1) / 2; g.TW = (g.W + 1) / 2;
-    const int64_t T = B * g.TH * g.TW;
-    FFWM_REQUIRE(T < (1LL << 30), FFWM_ERR_SIZE, "%s: too many tiles", fn);
-    g.T = static_cast<int>(T);
-    g.CH = (g.C + 7) / 8;
-    g.KT = (g.K + 63) / 64;
-    g.TT = (g.T + kWinoTiles - 1) / kWinoTiles;
-    g.act = act; g.slope = static_cast<float>(slope);
-    g.x_bytes = static_cast<unsigned>(B * C * H * W * 4);
+    const WinoPlan p = wino_plan(B, C, H, W, K, act, W % 4 == 0);
+    FFWM_REQUIRE(p.T < (1LL << 30), FFWM_ERR_SIZE, "%s: too many tiles", fn);
     const int64_t ub = ffwm_conv3x3_winograd_workspace_bytes(K, C);
     FFWM_REQUIRE(ub < (1LL << 31), FFWM_ERR_SIZE, "%s: weight workspace beyond 2 GiB", fn);
+    WinoGeo g = p.g;
+    g.slope = static_cast<float>(slope);
+    g.x_bytes = static_cast<unsigned>(B * C * H * W * 4);
     g.u_bytes = static_cast<unsigned>(ub);
     hipStream_t st = static_cast<hipStream_t>(stream);
+    const float* x = static_cast<const float*>(input);
+    const float* bs = static_cast<const float*>(bias);
     float* U = static_cast<float*>(workspace);
+    float* o = static_cast<float*>(output);
     if (!reuse) {
-        const int64_t n = static_cast<int64_t>(g.KT) * 64 * g.CH * 8 + (thin ? C * kThinStride : 0);
-        LaunchScope ls("conv_winograd_weights", st, 4.0 * (9.0 * K * C + 16.0 * n));
-        hipLaunchKernelGGL(winograd_weights_kernel, dim3(static_cast<unsigned>((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                           static_cast<const float*>(weight), U, g.K, static_cast<int>(K), g.C, g.CH, g.KT, data_gradient, thin ? tail : 0);
-        const int rc = check_launch(fn);
-        if (rc) return rc;
+        LaunchScope ls("conv_winograd_weights", st, 4.0 * (9.0 * K * C + 16.0 * p.ch.elems));
+        hipLaunchKernelGGL(winograd_weights_kernel, dim3(static_cast<unsigned>((p.ch.elems + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+                           static_cast<const float*>(weight), U, g.K, g.Kout, g.C, g.CH, g.KT, data_gradient, p.ch.tail);
+        if (int rc = check_launch(fn)) return rc;
     }
     if (g.KT > 0) {
         // flops = the multiplications the MFMAs actually perform (16 per tile, channel pair), not the 36 of the direct sum
-        const double flops = 2.0 * 16.0 * static_cast<double>(T) * g.K * C;
+        const double flops = 2.0 * 16.0 * static_cast<double>(p.T) * g.K * C;
         const double bytes = 4.0 * (static_cast<double>(B) * C * H * W + static_cast<double>(B) * g.K * H * W) + static_cast<double>(ub);
-        const unsigned nblk = static_cast<unsigned>(g.TT) * static_cast<unsigned>(g.KT);
-        // whole tile rows of one image per workgroup -> the raw-staged variant
-        const bool rawv = options().conv_wino_raw && (W == 16 || W == 32 || W == 64 || W == 128) && H % 2 == 0 && g.TW <= 64 && 64 % g.TW == 0 &&
-                          g.TH % (64 / g.TW) == 0 && (2 * (64 / g.TW) + 2) * g.W * 8 <= kWinoRawFloats;
-        g.R = rawv ? 64 / g.TW : 0;
-        g.ROWS = 2 * g.R + 2;
-        int split_n = 1;
-        if (rawv) {
-            split_n = winograd_splits(static_cast<int>(nblk), g.CH, act, device_cus());
-        }
+        const bool split = p.split_n > 1;
         // (a split call -- zero-fill + atomics, few pairs -- is a launch configuration of its own: its own profiling scope)
-        LaunchScope ls(split_n > 1 ? (data_gradient ? "conv_winograd_dgrad_split" : "conv_winograd_fwd_split")
-                                : (data_gradient ? "conv_winograd_dgrad" : "conv_winograd_fwd"), st, bytes, flops);
-        if (split_n > 1 && zero_fill(output, static_cast<size_t>(B) * K * H * W * 4, st)) return FFWM_ERR_LAUNCH;
-        if (rawv) {
-            auto kern = split_n > 1 ? winograd_conv_raw_kernel<true> : winograd_conv_raw_kernel<false>;
-            const int cus = device_cus();
-            const unsigned units = nblk * static_cast<unsigned>(split_n);
-            const unsigned pgrid = units < static_cast<unsigned>(cus) ? units : static_cast<unsigned>(cus);     // persistent: one workgroup per CU
-            if (split_n == 1 && options().conv_wino_ws) {
-                auto wsk = winograd_conv_ws_kernel;
-                allow_large_lds(reinterpret_cast<const void*>(wsk));
-                hipLaunchKernelGGL(wsk, dim3(pgrid), dim3(kWsThreads), 4 * kWinoChunk * 4 + 2 * kWinoRawFloats * 4, st,
-                                   static_cast<const float*>(input), U, static_cast<const float*>(bias), static_cast<float*>(output), g, options().xcd_remap);
-                const int rc = check_launch(fn);
-                if (rc || !thin) return rc;
-            } else {
+        LaunchScope ls(split ? (data_gradient ? "conv_winograd_dgrad_split" : "conv_winograd_fwd_split")
+                             : (data_gradient ? "conv_winograd_dgrad" : "conv_winograd_fwd"), st, bytes, flops);
+        if (split && zero_fill(output, static_cast<size_t>(B) * K * H * W * 4, st)) return FFWM_ERR_LAUNCH;
+        auto launch = [&](auto kern, unsigned grid, int threads, size_t lds, auto... more) {
             allow_large_lds(reinterpret_cast<const void*>(kern));
-            hipLaunchKernelGGL(kern, dim3(pgrid), dim3(kWinoThreads), 4 * kWinoChunk * 4 + 2 * kWinoRawFloats * 4, st, static_cast<const float*>(input), U,
-                               static_cast<const float*>(bias), static_cast<float*>(output), g, options().xcd_remap, split_n, g.CH / split_n);
-            const int rc = check_launch(fn);
-            if (rc || !thin) return rc;
-            }
-        } else {
-        auto kern = winograd_conv_kernel;
-        allow_large_lds(reinterpret_cast<const void*>(kern));
-        hipLaunchKernelGGL(kern, dim3(nblk), dim3(kWinoThreads), 4 * kWinoChunk * 4, st, static_cast<const float*>(input), U,
-                           static_cast<const float*>(bias), static_cast<float*>(output), g, options().xcd_remap);
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, x, U, bs, o, g, options().xcd_remap, more...);
+        };
+        constexpr size_t kOperands = 4 * kWinoChunk * 4, kRawWindows = 2 * kWinoRawFloats * 4;      // bytes of dynamic LDS
+        const unsigned nblk = static_cast<unsigned>(p.pairs), cus = static_cast<unsigned>(device_cus());
+        const unsigned units = nblk * static_cast<unsigned>(p.split_n);
+        const unsigned pgrid = units < cus ? units : cus;      // the raw-staged kernels are persistent: one workgroup per CU
+        if (!p.raw)
+            launch(winograd_conv_kernel, nblk, kWinoThreads, kOperands);
+        else if (!split && options().conv_wino_ws)
+            launch(winograd_conv_ws_kernel, pgrid, kWsThreads, kOperands + kRawWindows);
+        else
+            dispatch<false, true>(split, [&](auto SPLIT) {
+                launch(winograd_conv_raw_kernel<SPLIT.value>, pgrid, kWinoThreads, kOperands + kRawWindows, p.split_n, g.CH / p.split_n);
+            });
         const int rc = check_launch(fn);
-        if (rc || !thin) return rc;
-        }
+        if (rc || !p.ch.tail) return rc;
     }
     ThinGeo t;
     t.C = g.C; t.H = g.H; t.W = g.W; t.Kout = g.Kout; t.k_off = g.K;
     t.strips = static_cast<int>(B * H * W / 4);
-    t.act = act; t.slope = static_cast<float>(slope);
+    t.act = act; t.slope = g.slope;
     t.x_bytes = g.x_bytes;
-    LaunchScope ls("conv3x3_thin_tail", st, 4.0 * (static_cast<double>(B) * C * H * W + static_cast<double>(B) * tail * H * W));
-    const dim3 grid(static_cast<unsigned>((t.strips + 63) / 64)), block(64 * kThinWaves);
-    const float* xin = static_cast<const float*>(input);
+    LaunchScope ls("conv3x3_thin_tail", st, 4.0 * (static_cast<double>(B) * C * H * W + static_cast<double>(B) * p.ch.tail * H * W));
     const float* wt = U + static_cast<size_t>(g.KT) * g.CH * kWinoChunk;
-    const float* bs = static_cast<const float*>(bias);
-    float* o = static_cast<float*>(output);
-    switch (tail) {
-        case 1: hipLaunchKernelGGL(conv3x3_thin_kernel<1>, grid, block, 0, st, xin, wt, bs, o, t); break;
-        case 2: hipLaunchKernelGGL(conv3x3_thin_kernel<2>, grid, block, 0, st, xin, wt, bs, o, t); break;
-        case 3: hipLaunchKernelGGL(conv3x3_thin_kernel<3>, grid, block, 0, st, xin, wt, bs, o, t); break;
-        default: hipLaunchKernelGGL(conv3x3_thin_kernel<4>, grid, block, 0, st, xin, wt, bs, o, t); break;
-    }
-    return check_launch(fn);
+    const bool ok = dispatch<1, 2, 3, 4>(p.ch.tail, [&](auto KN) {
+        hipLaunchKernelGGL(conv3x3_thin_kernel<KN.value>, dim3(static_cast<unsigned>((t.strips + 63) / 64)), dim3(64 * kThinWaves), 0, st, x, wt, bs, o, t);
+    });
+    return ok ? check_launch(fn) : no_kernel(fn);
 }

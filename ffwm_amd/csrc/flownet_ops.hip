@@ -306,17 +306,22 @@ extern "C" int ffwm_bias_act_forward(const void* h, const void* bias, void* y, v
                      (!y2 || (reinterpret_cast<uintptr_t>(y2) % 16 == 0 && y2_batch_stride % 4 == 0));
     const int64_t total = B * C * HW / (vec ? 4 : 1);
     LaunchScope ls("flownet_bias_act", st, 4.0 * B * C * HW * (1.0 + (y ? 1 : 0) + (y2 ? 1 : 0)));
-#define FFWM_BA(ACT, VEC)                                                                                              \
-    hipLaunchKernelGGL((bias_act_kernel<ACT, VEC>), dim3(ew_grid(total)), dim3(kBlock), 0, st, (const float*)h,        \
-                       (const float*)bias, (float*)y, (float*)y2, total, (int)C, (int)HW, y_batch_stride, y2_batch_stride, \
-                       (float)negative_slope)
-    if (vec) {
-        if (act == 0) FFWM_BA(0, 4); else if (act == 1) FFWM_BA(1, 4); else FFWM_BA(2, 4);
-    } else {
-        if (act == 0) FFWM_BA(0, 1); else if (act == 1) FFWM_BA(1, 1); else FFWM_BA(2, 1);
-    }
-#undef FFWM_BA
-    return check_launch(fn);
+    const bool ok = dispatch<0, 1, 2>(act, [&](auto ACT) {
+        return dispatch<4, 1>(vec ? 4 : 1, [&](auto VEC) {
+            hipLaunchKernelGGL((bias_act_kernel<ACT.value, VEC.value>), dim3(ew_grid(total)), dim3(kBlock), 0, st, (const float*)h,
+                               (const float*)bias, (float*)y, (float*)y2, total, (int)C, (int)HW, y_batch_stride, y2_batch_stride,
+                               (float)negative_slope);
+        });
+    });
+    return ok ? check_launch(fn) : no_kernel(fn);
+}
+
+// Pixels per block of the flow head, forward and backward: the widest tile that still gives ~100 blocks.  A head's C x 9 taps run
+// serially in C / (256 / P) steps per thread, and the 8 x 8 / 16 x 16 levels of FlowNet (256 / 128 channels, batch 6) had 6 / 24
+// blocks of 64 pixels walking 64 / 32 channels each.
+static int flow_head_tile(int64_t B, int64_t HW) {
+    auto blocks = [&](int64_t P) { return B * ((HW + P - 1) / P); };
+    return HW >= 64 && blocks(64) >= 96 ? 64 : (HW >= 16 && blocks(16) >= 96 ? 16 : 4);
 }
 
 extern "C" int ffwm_flow_head_forward(const void* x, const void* weight, const void* bias, void* y, int64_t B, int64_t C,
@@ -328,18 +333,12 @@ extern "C" int ffwm_flow_head_forward(const void* x, const void* weight, const v
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int64_t HW = H * W;
     LaunchScope ls("flownet_flow_head", st, 4.0 * (B * C * HW + 18.0 * C + 2.0 * B * HW));
-#define FFWM_FH(P)                                                                                                     \
-    do {                                                                                                               \
-        const int tiles = static_cast<int>((HW + P - 1) / P);                                                          \
-        hipLaunchKernelGGL((flow_head_kernel<P>), dim3(static_cast<unsigned>(B * tiles)), dim3(kBlock), 0, st,         \
-                           (const float*)x, (const float*)weight, (const float*)bias, (float*)y, (int)C, (int)H, (int)W, tiles); \
-    } while (0)
-    // the widest pixel tile that still gives ~100 blocks: a head's C x 9 taps run serially in C / (256 / P) steps per thread, and the
-    // 8 x 8 / 16 x 16 levels of FlowNet (256 / 128 channels, batch 6) had 6 / 24 blocks of 64 pixels walking 64 / 32 channels each
-    auto blocks = [&](int64_t P) { return B * ((HW + P - 1) / P); };
-    if (HW >= 64 && blocks(64) >= 96) FFWM_FH(64); else if (HW >= 16 && blocks(16) >= 96) FFWM_FH(16); else FFWM_FH(4);
-#undef FFWM_FH
-    return check_launch(fn);
+    const bool ok = dispatch<64, 16, 4>(flow_head_tile(B, HW), [&](auto P) {
+        const int tiles = static_cast<int>((HW + P.value - 1) / P.value);
+        hipLaunchKernelGGL((flow_head_kernel<P.value>), dim3(static_cast<unsigned>(B * tiles)), dim3(kBlock), 0, st,
+                           (const float*)x, (const float*)weight, (const float*)bias, (float*)y, (int)C, (int)H, (int)W, tiles);
+    });
+    return ok ? check_launch(fn) : no_kernel(fn);
 }
 
 extern "C" int ffwm_flow_up_forward(const void* flow, const void* weight, const void* bias, void* out, int64_t B, int64_t H,
@@ -368,18 +367,13 @@ extern "C" int ffwm_flow_head_backward(const void* y, const void* grad_y, const 
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int64_t HW = H * W;
     LaunchScope ls("flownet_flow_head_bwd", st, 4.0 * (B * C * HW + 18.0 * C + 6.0 * B * HW));
-#define FFWM_FHB(P)                                                                                                    \
-    do {                                                                                                               \
-        const int tiles = static_cast<int>((HW + P - 1) / P);                                                          \
-        hipLaunchKernelGGL((flow_head_bwd_kernel<P>), dim3(static_cast<unsigned>(B * tiles)), dim3(kBlock), 0, st,     \
-                           (const float*)y, (const float*)grad_y, (const float*)weight, (float*)grad_z, (float*)grad_x, (int)C, (int)H, \
-                           (int)W, tiles);                                                                             \
-    } while (0)
-    // (the forward's rule: the widest pixel tile that still gives ~100 blocks)
-    auto blocks = [&](int64_t P) { return B * ((HW + P - 1) / P); };
-    if (HW >= 64 && blocks(64) >= 96) FFWM_FHB(64); else if (HW >= 16 && blocks(16) >= 96) FFWM_FHB(16); else FFWM_FHB(4);
-#undef FFWM_FHB
-    return check_launch(fn);
+    const bool ok = dispatch<64, 16, 4>(flow_head_tile(B, HW), [&](auto P) {
+        const int tiles = static_cast<int>((HW + P.value - 1) / P.value);
+        hipLaunchKernelGGL((flow_head_bwd_kernel<P.value>), dim3(static_cast<unsigned>(B * tiles)), dim3(kBlock), 0, st,
+                           (const float*)y, (const float*)grad_y, (const float*)weight, (float*)grad_z, (float*)grad_x, (int)C, (int)H,
+                           (int)W, tiles);
+    });
+    return ok ? check_launch(fn) : no_kernel(fn);
 }
 
 // d(input) of ffwm_flow_up_forward: grad_out [B, 2, 2H, 2W] with batch stride grad_out_batch_stride (a channel slice of a
@@ -419,10 +413,11 @@ extern "C" int ffwm_conv_thin_forward(const void* x, const void* weight_ctk, con
     if (v & 3) kt = (v & 3) == 1 ? 8 : (K % 16 == 0 ? 16 : 8);
     const dim3 grid(static_cast<unsigned>((nseg + per - 1) / per), static_cast<unsigned>(K / kt));
     LaunchScope ls("flownet_conv_thin", st, 4.0 * (B * C * H * W + static_cast<double>(B) * K * H * W), 2.0 * B * H * W * K * C * 9);
-#define FFWM_CT2(KERNEL) hipLaunchKernelGGL(KERNEL, grid, dim3(kBlock), 0, st, (const float*)x, (const float*)weight_ctk, (const float*)bias, (float*)y, (int)C, \
-                       (int)H, (int)W, (int)K, segs_x, nseg, act, (float)negative_slope)
-    if (v & 4) { if (kt == 8) FFWM_CT2((conv3x3_direct_kernel<8, 1>)); else FFWM_CT2((conv3x3_direct_kernel<16, 1>)); }
-    else { if (kt == 8) FFWM_CT2((conv3x3_direct_kernel<8, 3>)); else FFWM_CT2((conv3x3_direct_kernel<16, 3>)); }
-#undef FFWM_CT2
-    return check_launch(fn);
+    const bool ok = dispatch<8, 16>(kt, [&](auto KT) {
+        return dispatch<3, 1>(v & 4 ? 1 : 3, [&](auto G) {          // input channels per step
+            hipLaunchKernelGGL((conv3x3_direct_kernel<KT.value, G.value>), grid, dim3(kBlock), 0, st, (const float*)x, (const float*)weight_ctk,
+                               (const float*)bias, (float*)y, (int)C, (int)H, (int)W, (int)K, segs_x, nseg, act, (float)negative_slope);
+        });
+    });
+    return ok ? check_launch(fn) : no_kernel(fn);
 }

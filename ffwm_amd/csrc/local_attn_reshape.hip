@@ -115,19 +115,10 @@ int launch_fwd(const T* in, T* out, int64_t B, int64_t H, int64_t W, int k, hipS
     const double bytes = 2.0 * sizeof(T) * static_cast<double>(nrows) * k;
     const unsigned grid = grid_for(nrows);
     LaunchScope ls("local_attn_reshape_fwd", st, bytes);
-#define FFWM_LAR_FWD(KK)                                                                          \
-    case KK:                                                                                      \
-        hipLaunchKernelGGL((lar_fwd_kernel<T, KK>), dim3(grid), dim3(kBlock), 0, st, in, out,      \
-                           nrows, (int)H, (int)W);                                                \
-        break;
-    switch (k) {
-        FFWM_LAR_FWD(1) FFWM_LAR_FWD(2) FFWM_LAR_FWD(3) FFWM_LAR_FWD(4) FFWM_LAR_FWD(5)
-        FFWM_LAR_FWD(6) FFWM_LAR_FWD(7)
-        default:
-            hipLaunchKernelGGL((lar_fwd_generic<T>), dim3(grid), dim3(kBlock), 0, st, in, out, nrows,
-                               (int)H, (int)W, k);
-    }
-#undef FFWM_LAR_FWD
+    if (!dispatch<1, 2, 3, 4, 5, 6, 7>(k, [&](auto KK) {
+            hipLaunchKernelGGL((lar_fwd_kernel<T, KK.value>), dim3(grid), dim3(kBlock), 0, st, in, out, nrows, (int)H, (int)W);
+        }))
+        hipLaunchKernelGGL((lar_fwd_generic<T>), dim3(grid), dim3(kBlock), 0, st, in, out, nrows, (int)H, (int)W, k);
     return check_launch("ffwm_local_attn_reshape_forward");
 }
 
@@ -138,23 +129,12 @@ int launch_bwd(const T* gout, T* gin, int64_t B, int64_t H, int64_t W, int k, in
     const double bytes = 2.0 * sizeof(T) * static_cast<double>(nrows) * k;
     const unsigned grid = grid_for(nrows);
     LaunchScope ls("local_attn_reshape_bwd", st, bytes);
-#define FFWM_LAR_BWD(KK)                                                                          \
-    case KK:                                                                                      \
-        if (acc)                                                                                  \
-            hipLaunchKernelGGL((lar_bwd_kernel<T, KK, true>), dim3(grid), dim3(kBlock), 0, st,     \
-                               gout, gin, nrows, (int)H, (int)W);                                 \
-        else                                                                                      \
-            hipLaunchKernelGGL((lar_bwd_kernel<T, KK, false>), dim3(grid), dim3(kBlock), 0, st,    \
-                               gout, gin, nrows, (int)H, (int)W);                                 \
-        break;
-    switch (k) {
-        FFWM_LAR_BWD(1) FFWM_LAR_BWD(2) FFWM_LAR_BWD(3) FFWM_LAR_BWD(4) FFWM_LAR_BWD(5)
-        FFWM_LAR_BWD(6) FFWM_LAR_BWD(7)
-        default:
-            hipLaunchKernelGGL((lar_bwd_generic<T>), dim3(grid), dim3(kBlock), 0, st, gout, gin, nrows,
-                               (int)H, (int)W, k, acc);
-    }
-#undef FFWM_LAR_BWD
+    if (!dispatch<1, 2, 3, 4, 5, 6, 7>(k, [&](auto KK) {
+            return dispatch<true, false>(acc != 0, [&](auto ACC) {
+                hipLaunchKernelGGL((lar_bwd_kernel<T, KK.value, ACC.value>), dim3(grid), dim3(kBlock), 0, st, gout, gin, nrows, (int)H, (int)W);
+            });
+        }))
+        hipLaunchKernelGGL((lar_bwd_generic<T>), dim3(grid), dim3(kBlock), 0, st, gout, gin, nrows, (int)H, (int)W, k, acc);
     return check_launch("ffwm_local_attn_reshape_backward");
 }
 
