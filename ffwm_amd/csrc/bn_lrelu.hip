@@ -146,7 +146,7 @@ bn_lrelu_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma
     const double n = static_cast<double>(g.B) * g.HW;
     const double mean = s / n;
     double var = ss / n - mean * mean;
-    var = var > 0 ? var : 0;
+    var = (var > 0 || var != var) ? var : 0;               // rounding may leave a tiny negative; a NaN (NaN or inf in the channel) stays
     const float invstd = static_cast<float>(1.0 / sqrt(var + static_cast<double>(g.eps)));
     const float meanf = static_cast<float>(mean);
     if (live && t == 0 && blockIdx.y == 0) {
