@@ -30,6 +30,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kCorRows = 32;          // source rows per tile
 constexpr int kCorCols = 128;         // target columns per workgroup (4 waves x 32)
 
+// max that propagates NaN, as torch.max does: a NaN candidate replaces the running value, and a NaN running value is never replaced
+// (every comparison with it is false)
+__device__ __forceinline__ float nan_max(float m, float a) { return (a > m || a != a) ? a : m; }
+
 template <int KC>                     // KC = C / 64
 __global__ void __launch_bounds__(kBlock)
 corr_colmax_kernel(const float* __restrict__ src, const float* __restrict__ tgt, float* __restrict__ out, int N,
@@ -75,7 +79,7 @@ corr_colmax_kernel(const float* __restrict__ src, const float* __restrict__ tgt,
 
     float m[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) m[r] = -3.0e38f;
+    for (int r = 0; r < 16; ++r) m[r] = -INFINITY;
     const int ntiles = (N + kCorRows - 1) / kCorRows;
     fetch(0);
     commit(tile_mem);
@@ -97,8 +101,9 @@ corr_colmax_kernel(const float* __restrict__ src, const float* __restrict__ tgt,
             for (int kk = 0; kk < 32; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(areg[kk], breg[ch * 32 + kk], acc, 0, 0, 0);
         }
         // (rows past N in a ragged last tile are clamped copies of row N-1: harmless for a max)
+        // torch.max semantics: a NaN product sticks (fmaxf would drop it), and the maxima start at -inf so that a column of -inf stays -inf
 #pragma unroll
-        for (int r = 0; r < 16; ++r) m[r] = fmaxf(m[r], acc[r]);
+        for (int r = 0; r < 16; ++r) m[r] = nan_max(m[r], acc[r]);
         if (t + 1 < ntiles) commit(tile_mem + (p ^ 1) * (kCorRows * PITCH));
         __syncthreads();
     }
@@ -106,8 +111,8 @@ corr_colmax_kernel(const float* __restrict__ src, const float* __restrict__ tgt,
     // disjoint rows of the same column
     float best = m[0];
 #pragma unroll
-    for (int r = 1; r < 16; ++r) best = fmaxf(best, m[r]);
-    best = fmaxf(best, __shfl_xor(best, 32, kWave));
+    for (int r = 1; r < 16; ++r) best = nan_max(best, m[r]);
+    best = nan_max(best, __shfl_xor(best, 32, kWave));
     const int jc = j0 + wave * 32 + l31;
     if (half == 0 && jc < N) out[static_cast<size_t>(b) * N + jc] = best;
 }

@@ -112,7 +112,7 @@ sn_phase2_kernel(SnFwdArgs a, int power_iterations, T eps) {     // wv[i] = sum_
     T nrm = 1;
     if (power_iterations) {              // v still holds v_raw: normalise on the fly
         nrm = sqrt(block_sumsq(v, L.cols, red));
-        nrm = nrm > eps ? nrm : eps;     // F.normalize: x / max(||x||, eps)
+        nrm = nrm < eps ? eps : nrm;     // F.normalize: x / max(||x||, eps); a NaN norm stays NaN, as torch's clamp_min keeps it
     }
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     for (int r = wave; r < kRowChunk; r += kSnWaves) {
@@ -145,7 +145,7 @@ sn_phase3_kernel(SnFwdArgs a, int power_iterations, T eps) {
     if (power_iterations) {
         // u = wv / max(|wv|, eps);  sigma = u . wv
         T nrm = sqrt(block_sumsq(wv, L.rows, red));
-        unrm = nrm > eps ? nrm : eps;
+        unrm = nrm < eps ? eps : nrm;
         T p = 0;
         for (int i = threadIdx.x; i < L.rows; i += kSnBlock) p += (wv[i] / unrm) * wv[i];
         sigma = block_sum(p, red);
@@ -158,7 +158,7 @@ sn_phase3_kernel(SnFwdArgs a, int power_iterations, T eps) {
         T vinv_nrm = 1;
         if (power_iterations) {
             T nrm = sqrt(block_sumsq(v, L.cols, red));
-            vinv_nrm = nrm > eps ? nrm : eps;
+            vinv_nrm = nrm < eps ? eps : nrm;
         }
         __syncthreads();                 // every thread has read v_raw before anyone overwrites it
         T* us = static_cast<T*>(L.u_saved);
