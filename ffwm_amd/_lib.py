@@ -66,6 +66,7 @@ _SIGNATURES = {
     "ffwm_guided_filter_forward": [_p, _p, _p, _p, _i64, _i64, _i64, _i, ctypes.c_double, _i, _p],
     "ffwm_affine_regularization": [_p, _p, _p, _p, _i64, _i64, _i64, _i, ctypes.c_double, _i, _p],
     "ffwm_correlation_colmax": [_p, _p, _p, _i64, _i64, _i64, _i, _p],
+    "ffwm_sampling_correctness": [_p] * 9 + [_i64] * 6 + [ctypes.c_double, ctypes.c_double, _i, _p],
     "ffwm_guided_filter_backward": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i, _i, _p],
     "ffwm_guided_filter_forward_general": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, ctypes.c_double, _i, _p],
     "ffwm_guided_filter_backward_general": [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, _i, _p],
@@ -84,7 +85,8 @@ _SIGNATURES = {
 }
 
 EXPORTS = sorted(list(_SIGNATURES) + ["ffwm_last_error", "ffwm_conv3x3_winograd_workspace_bytes", "ffwm_conv3x3_winograd_splits",
-                                      "ffwm_conv2d_forward_workspace", "ffwm_guided_filter_workspace_bytes"])
+                                      "ffwm_conv2d_forward_workspace", "ffwm_guided_filter_workspace_bytes",
+                                      "ffwm_sampling_correctness_workspace_bytes"])
 
 
 class FFWMError(RuntimeError):
@@ -113,6 +115,8 @@ def load():
     lib.ffwm_conv2d_forward_workspace.restype = _i64
     lib.ffwm_guided_filter_workspace_bytes.argtypes = [_i64] * 4 + [_i, _i]
     lib.ffwm_guided_filter_workspace_bytes.restype = _i64
+    lib.ffwm_sampling_correctness_workspace_bytes.argtypes = [_i64, _i64, _i64, _i]
+    lib.ffwm_sampling_correctness_workspace_bytes.restype = _i64
     lib.ffwm_last_error.argtypes = []
     lib.ffwm_last_error.restype = ctypes.c_char_p
     got = lib.ffwm_abi_version()

@@ -32,6 +32,25 @@ class _FusedAffineReg(Function):
         return (grad * grad_output if grad is not None else None), None, None
 
 
+class _FusedSamplingCorrectness(Function):
+    """The correctness loss of one scale and d(loss)/d(flow) from one call (csrc/sampling_correctness.hip); the features, the
+    correlation maximum and the mask get no gradient."""
+
+    @staticmethod
+    def forward(ctx, flow, source, target, corr_max, mask, eps):
+        out, grad, _ = ops.sampling_correctness(source, target, flow, corr_max, mask, eps, want_grad=ctx.needs_input_grad[0])
+        if grad is not None:
+            ctx.save_for_backward(grad, out)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        if not ctx.saved_tensors:
+            return (None,) * 6
+        grad, out = ctx.saved_tensors
+        return (grad * (grad_output / out[1]), None, None, None, None, None)
+
+
 def affine_residual_kernels(kz):
     """The kz^2 filters [kz^2, 1, kz, kz] (float64) whose responses, dotted with a window of the sampling grid, give the squared
     distance of that window from the nearest affine map (what losses.py:192-199 builds).  With the design matrix D of the window's
@@ -168,10 +187,12 @@ class PerceptualCorrectness(nn.Module):
     the flow, and neither the images nor VGG are trained, so they are evaluated under no_grad -- the
     reference back-propagates through a [B, N^2, N^2] matrix (1 GiB per sample at relu1_1) for nothing."""
 
-    def __init__(self, vgg, warp, layer=("relu1_1", "relu2_1", "relu3_1", "relu4_1"), resample=None):
+    def __init__(self, vgg, warp, layer=("relu1_1", "relu2_1", "relu3_1", "relu4_1"), resample=None, fused=False):
         super().__init__()
         self.vgg = vgg
         self.warp = warp
+        # True: warp, cosine, exp, mask and the sums of a scale as one HIP kernel (csrc/sampling_correctness.hip) wherever it applies
+        self.fused = fused
         self.layer = list(layer)
         self.eps = 1e-8
         # losses.py:329: the Gaussian-weighted resampler of the `use_bilinear_sampling=False` branch (the one call site
@@ -202,6 +223,12 @@ class PerceptualCorrectness(nn.Module):
                 correction_max = ops.correlation_colmax(source_norm, target_norm)   # MFMA, no [b, N2, N2] matrix
             else:
                 correction_max = torch.bmm(source_norm, target_norm).max(dim=1)[0]  # [b, N2]
+        if self._takes_kernel(flow, source_vgg, target_vgg, use_bilinear_sampling):
+            mask = None
+            if norm_mask is not None:
+                mask = F.interpolate(norm_mask, size=(h, w)).reshape(-1, h * w).to(flow.dtype).contiguous()
+            return _FusedSamplingCorrectness.apply(flow.contiguous(), source_vgg.contiguous(), target_vgg.contiguous(),
+                                                   correction_max.contiguous(), mask, self.eps)
         if use_bilinear_sampling:                                                  # losses.py:356-357
             input_sample = self.warp(source_vgg, flow).reshape(b, c, -1)
         else:                                                                      # losses.py:358-359 -> resample2d
@@ -213,6 +240,15 @@ class PerceptualCorrectness(nn.Module):
             return torch.mean(loss_map) - e1
         norm_mask = F.interpolate(norm_mask, size=(h, w)).reshape(-1, h * w)
         return (torch.sum(norm_mask * loss_map) - e1) / (torch.sum(norm_mask) + self.eps)
+
+    def _takes_kernel(self, flow, source_vgg, target_vgg, use_bilinear_sampling):
+        """The fused kernel serves the bilinear branch on float32 / float64 GPU tensors when only the flow wants a gradient (the
+        features' gradient exists in the composition alone); the resample2d branch stays composed."""
+        if not (self.fused and use_bilinear_sampling and flow.is_cuda and source_vgg.is_cuda and target_vgg.is_cuda):
+            return False
+        if flow.dtype not in (torch.float32, torch.float64) or source_vgg.dtype != flow.dtype or target_vgg.dtype != flow.dtype:
+            return False
+        return not (source_vgg.requires_grad or target_vgg.requires_grad)
 
 
 _E1 = {}

@@ -481,6 +481,54 @@ def correlation_colmax(source, target):
     return out
 
 
+# ---------------------------------------------------------------- fused sampling-correctness loss
+def sampling_correctness(source, target, flow, corr_max, mask, eps, want_grad, want_map=False):
+    """-> (out[2], grad_flow or None, loss_map or None): PerceptualCorrectness.calculate_loss of the reference (losses.py:341-371,
+    bilinear branch) after the correlation maximum, one pass (csrc/sampling_correctness.hip).  source [B,C,Hi,Wi], target [B,C,H,W],
+    flow [B,2,H,W], corr_max [B,H W], mask [B,H W] or None.  out[0] is the loss, out[1] the denominator of its mean;
+    grad_flow = mask d(loss_map)/d(flow), to be scaled by grad_output / out[1]."""
+    name = "sampling_correctness"
+    _check(name, source, target, flow)
+    B, C, Hi, Wi = source.shape
+    H, W = target.shape[2:]
+    if target.shape[:2] != (B, C) or tuple(flow.shape) != (B, 2, H, W):
+        raise ValueError("%s: need source [B,C,Hi,Wi], target [B,C,H,W] and flow [B,2,H,W], got %s, %s, %s"
+                         % (name, tuple(source.shape), tuple(target.shape), tuple(flow.shape)))
+    for t, what in ((corr_max, "corr_max"), (mask, "mask")):
+        if t is None:
+            continue
+        if not t.is_cuda or t.device != source.device:
+            raise ValueError("%s: %s must live on the operands' device" % (name, what))
+        if t.dtype != source.dtype:
+            raise TypeError("%s: mixed dtypes (%s vs %s)" % (name, t.dtype, source.dtype))
+        if t.numel() != B * H * W or not t.is_contiguous():
+            raise ValueError("%s: %s must be a contiguous [B, H W] tensor" % (name, what))
+    if corr_max is None:
+        raise ValueError("%s: corr_max is required" % name)
+    code = _dtype_code(source)
+    from .losses import _exp_minus_one
+    e1 = _exp_minus_one(source.dtype)
+    out = source.new_empty(2)
+    grad = torch.empty_like(flow) if want_grad else None
+    loss_map = source.new_empty((B, H * W)) if want_map else None
+    if B * H * W == 0 or C == 0:
+        # nothing to launch: the value the composition gives an empty grid (the mean of nothing is NaN; an empty mask sums to 0)
+        zero = source.new_zeros(())
+        out[0] = float("nan") if mask is None else (zero - e1) / (zero + eps)
+        out[1] = 0.0 if mask is None else eps
+        if grad is not None:
+            grad.zero_()
+        return out, grad, loss_map
+    n = _lib.load().ffwm_sampling_correctness_workspace_bytes(B, H, W, code)
+    _lib.check(min(n, 0), "ffwm_sampling_correctness_workspace_bytes")
+    ws = torch.empty(n // 8, dtype=torch.float64, device=source.device)
+    with _on_device(source) as stream:
+        _lib.check(_lib.load().ffwm_sampling_correctness(
+            _ptr(source), _ptr(target), _ptr(flow), _ptr(corr_max), _ptr(mask), _ptr(loss_map), _ptr(grad), _ptr(out), _ptr(ws),
+            B, C, Hi, Wi, H, W, e1, float(eps), code, stream), "ffwm_sampling_correctness")
+    return out, grad, loss_map
+
+
 # ---------------------------------------------------------------- conv weight gradient (MFMA)
 def conv3x3_wgrad_supported(input, grad_output):
     """Shapes the MFMA weight-gradient kernel takes: float32 NCHW, W a multiple of 64, below 4 GiB."""

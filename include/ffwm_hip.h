@@ -18,6 +18,7 @@
  *   ffwm_guided_filter_*            <- GuidedFilter.forward             models/external_function.py:239-277
  *   ffwm_affine_regularization      <- AffineRegularizationLoss.__call__ models/losses.py:200-219
  *   ffwm_correlation_colmax         <- max(bmm(source, target), dim=1)  models/losses.py:347-353
+ *   ffwm_sampling_correctness       <- PerceptualCorrectness.calculate_loss (warp, cosine, exp, mask, sums)  models/losses.py:341-371
  *   ffwm_block_attention_*          <- avg_pool2d(BlockExtractor * LocalAttnReshape)  (composition of the ops above)
  *   ffwm_spectral_norm_*            <- torch.nn.utils.spectral_norm hooks models/base_networks.py:5,218-264,381-413
  *   ffwm_conv3x3_wgrad[_block]      <- convolution_backward grad_weight / grad_bias of the nn.Conv2d(., ., 3, 1, 1) layers
@@ -301,6 +302,35 @@ int ffwm_affine_regularization(const void* flow, const void* ktk, void* loss_sum
  * source[B,N,C], target[B,C,N] contiguous float32, C in {64, 128, 256}, out[B,N]. */
 int ffwm_correlation_colmax(const void* source, const void* target, void* out, int64_t B, int64_t N,
                             int64_t C, int dtype, void* stream);
+
+/* ---- fused sampling-correctness loss (FlowNet pre-training) -------------------------------------
+ * PerceptualCorrectness.calculate_loss of models/losses.py:341-371 on its bilinear branch (:356-357), for one flow scale, after
+ * the correlation maximum: grid_sample -> cosine_similarity -> exp -> mask -> sums, and the gradient for the flow, in ONE pass
+ * over the channels (plus a one-block launch that adds the per-block sums in a fixed order).  Per pixel p = (b, y, x):
+ *   the sampling position px = ((flow[b,0,p] + 1) Wi - 1) / 2, py likewise with Hi, and its four taps are those of
+ *   ffwm_warp_forward (ATen grid_sampler_2d, bilinear / zeros / align_corners=False); an out-of-range tap counts as the value 0
+ *   in the sample s_c and in its derivatives dx s_c = (1 - ty)(v01 - v00) + ty (v11 - v10), dy s_c likewise;
+ *   D = sum_c s_c t_c, S = sum s_c^2, T = sum t_c^2, Px = sum t_c dx s_c, Qx = sum s_c dx s_c (Py, Qy likewise);
+ *   ns = max(sqrt S, 1e-8), nt = max(sqrt T, 1e-8), cos = D / (ns nt)       (F.cosine_similarity: each norm clamped)
+ *   m = exp(-cos / (corr_max[p] + eps))
+ *   d m / d flow_x = -m / (corr_max[p] + eps) (Px / (ns nt) - [sqrt S > 1e-8] D Qx / (ns^3 nt)) Wi / 2     (y: Py, Qy, Hi / 2)
+ * source[B,C,Hi,Wi], target[B,C,H,W], flow[B,2,H,W] (normalised absolute coordinates, ch0 = x), corr_max[B,H W],
+ * mask[B,H W] or NULL (= all ones).  Outputs, all OVERWRITTEN with plain stores (one owner per pixel, no atomics):
+ *   loss_map[B,H W] = m                              (NULL: not written)
+ *   grad_flow[B,2,H,W] = mask d m / d flow           (NULL: not written); the caller scales it by grad_output / out[1]
+ *   out[0] = (sum mask m - e1) / (sum mask + eps)    with a mask,    sum m / (B H W) - e1    without
+ *   out[1] = sum mask + eps                          with a mask,    B H W                   without
+ * e1 = exp(-1) rounded in the tensors' dtype, eps = the module's 1e-8.  The sums over the pixels are formed in double, per block
+ * into `workspace` (ffwm_sampling_correctness_workspace_bytes(B, H, W, dtype) bytes, 8-byte aligned, contents irrelevant on entry
+ * and exit; a negative ffwm_status for sizes the entry point refuses) and then in a fixed order: two calls agree bit for bit.
+ * C >= 1 is arbitrary, Hi x Wi independent of H x W; a plane of 2^28 elements or more, or C Hi Wi elements of 4 GiB or more, is
+ * FFWM_ERR_SIZE.  A non-finite flow samples nothing (m = 1, gradient 0) where the composition yields NaN: the entry point follows
+ * the composition only where that is defined. */
+int64_t ffwm_sampling_correctness_workspace_bytes(int64_t B, int64_t H, int64_t W, int dtype);
+int ffwm_sampling_correctness(const void* source, const void* target, const void* flow, const void* corr_max,
+                              const void* mask, void* loss_map, void* grad_flow, void* out, void* workspace,
+                              int64_t B, int64_t C, int64_t Hi, int64_t Wi, int64_t H, int64_t W, double e1,
+                              double eps, int dtype, void* stream);
 
 /* Fused extractor + attention consumer (the GFLA-style local attention the cfg-5 shape
  * models): what the reference API can only express as

@@ -212,6 +212,41 @@ def main():
             ms = (time.perf_counter() - t0) / args.reps * 1e3
             results.append({"case": "MultiAffineRegularizationLoss fwd+bwd bs=6 (3 scales), %s" % ("fused kernel" if fused else "op composition"),
                             "kernel": "wall", "avg_ms": round(ms, 4)})
+    if want("correctness"):
+        # PerceptualCorrectness.calculate_loss with a mask at the three scales of FlowNet pre-training (bs 6; relu3_1 / relu2_1 / relu1_1
+        # of 128 px images), forward + backward: the warp + cosine + exp composition vs the fused kernel (csrc/sampling_correctness.hip).
+        # Wall time as the affine case takes it, then one profiled pass for the library's launch counts and per-kernel times (the
+        # correlation maximum in front is common to both paths).
+        import time
+        from ffwm_amd.external_function import WarpNet
+        from ffwm_amd.losses import PerceptualCorrectness
+        mask = (torch.rand(6, 1, 128, 128, generator=g) < 0.6).float().to(dev)
+        for (C, S) in ((256, 32), (128, 64), (64, 128)):
+            src = (torch.rand(6, C, S, S, generator=g) + 0.1).to(dev)
+            tgt = (torch.rand(6, C, S, S, generator=g) + 0.1).to(dev)
+            fl = make_flow(6, S).requires_grad_(True)
+            for fused in (False, True):
+                pc = PerceptualCorrectness(None, WarpNet(), fused=fused)
+                pc.target_vgg, pc.source_vgg = {"x": tgt}, {"x": src}
+
+                def step():
+                    fl.grad = None
+                    pc.calculate_loss(fl, "x", mask, use_bilinear_sampling=True).backward()
+                for _ in range(5):
+                    step()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(args.reps):
+                    step()
+                torch.cuda.synchronize()
+                ms = (time.perf_counter() - t0) / args.reps * 1e3
+                name = "correctness loss fwd+bwd [6,%d,%d,%d] flow=%s, %s" % (C, S, S, args.warp_flow, "fused kernel" if fused else "op composition")
+                results.append({"case": name, "kernel": "wall", "avg_ms": round(ms, 4)})
+                rows = run(name, step, args.reps)
+                lib_launches = sum(r.get("launches", 0) for r in rows) / float(args.reps)
+                results += rows
+                results.append({"case": name, "kernel": "(library launches per call)", "launches_per_call": lib_launches})
+            del src, tgt, fl
     for r in results:
         print(json.dumps(r))
 
