@@ -66,6 +66,7 @@ _SIGNATURES = {
     "ffwm_guided_filter_forward": [_p, _p, _p, _p, _i64, _i64, _i64, _i, ctypes.c_double, _i, _p],
     "ffwm_affine_regularization": [_p, _p, _p, _p, _i64, _i64, _i64, _i, ctypes.c_double, _i, _p],
     "ffwm_correlation_colmax": [_p, _p, _p, _i64, _i64, _i64, _i, _p],
+    "ffwm_correlation_colmax_split": [_p, _p, _p, _i64, _i64, _i64, _i, _p],
     "ffwm_sampling_correctness": [_p] * 9 + [_i64] * 6 + [ctypes.c_double, ctypes.c_double, _i, _p],
     "ffwm_guided_filter_backward": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i, _i, _p],
     "ffwm_guided_filter_forward_general": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, ctypes.c_double, _i, _p],

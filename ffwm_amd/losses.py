@@ -187,8 +187,12 @@ class PerceptualCorrectness(nn.Module):
     the flow, and neither the images nor VGG are trained, so they are evaluated under no_grad -- the
     reference back-propagates through a [B, N^2, N^2] matrix (1 GiB per sample at relu1_1) for nothing."""
 
-    def __init__(self, vgg, warp, layer=("relu1_1", "relu2_1", "relu3_1", "relu4_1"), resample=None, fused=False):
+    def __init__(self, vgg, warp, layer=("relu1_1", "relu2_1", "relu3_1", "relu4_1"), resample=None, fused=False,
+                 corr_precision="fp32"):
         super().__init__()
+        # "bf16x3": the correlation maximum of the MFMA branch on the bf16 matrix instruction with hi/lo-split operands
+        # (ops.correlation_colmax); the bmm + max branch (small grids, CPU, float64) is the same whatever is asked
+        self.corr_precision = ops.check_corr_precision(corr_precision, "PerceptualCorrectness")
         self.vgg = vgg
         self.warp = warp
         # True: warp, cosine, exp, mask and the sums of a scale as one HIP kernel (csrc/sampling_correctness.hip) wherever it applies
@@ -218,9 +222,9 @@ class PerceptualCorrectness(nn.Module):
             source_all = source_vgg.reshape(b, c, -1).transpose(1, 2)   # [b, N2, C]
             source_norm = source_all / (source_all.norm(dim=2, keepdim=True) + self.eps)
             target_norm = target_all / (target_all.norm(dim=1, keepdim=True) + self.eps)
-            # (the MFMA kernel wants >= 192 workgroups of 128 columns; below that rocBLAS + max is as fast)
+            # (the MFMA kernels want >= 192 workgroups of 128 columns, both precisions; below that rocBLAS + max is as fast)
             if source_norm.is_cuda and source_norm.dtype == torch.float32 and c in (64, 128, 256) and b * ((h * w + 127) // 128) >= 192:
-                correction_max = ops.correlation_colmax(source_norm, target_norm)   # MFMA, no [b, N2, N2] matrix
+                correction_max = ops.correlation_colmax(source_norm, target_norm, precision=self.corr_precision)   # MFMA, no [b, N2, N2] matrix
             else:
                 correction_max = torch.bmm(source_norm, target_norm).max(dim=1)[0]  # [b, N2]
         if self._takes_kernel(flow, source_vgg, target_vgg, use_bilinear_sampling):

@@ -463,8 +463,20 @@ def affine_regularization(flow, ktk, kernel_size, want_grad=True):
 
 
 # ---------------------------------------------------------------- correlation column maximum (MFMA)
-def correlation_colmax(source, target):
-    """torch.bmm(source[B,N,C], target[B,C,N]).max(dim=1)[0] without the [B,N,N] matrix (losses.py:347-353)."""
+CORR_PRECISIONS = ("fp32", "bf16x3")
+
+
+def check_corr_precision(precision, who="correlation_colmax"):
+    if precision not in CORR_PRECISIONS:
+        raise ValueError("%s: precision must be one of %s, got %r" % (who, ", ".join(CORR_PRECISIONS), precision))
+    return precision
+
+
+def correlation_colmax(source, target, precision="fp32"):
+    """torch.bmm(source[B,N,C], target[B,C,N]).max(dim=1)[0] without the [B,N,N] matrix (losses.py:347-353).
+    precision "fp32": the fp32 MFMA kernel; "bf16x3": the bf16 MFMA kernel on hi/lo-split operands, three MFMAs per k-block
+    (csrc/correlation.hip: error (2^-16 + 3 C roundings) sum |s t|; an infinite operand counts as a NaN)."""
+    check_corr_precision(precision)
     if source.dim() != 3 or target.dim() != 3 or source.size(0) != target.size(0) or source.size(1) != target.size(2) \
             or source.size(2) != target.size(1):
         raise ValueError("correlation_colmax: need source [B,N,C] and target [B,C,N]")
@@ -476,8 +488,8 @@ def correlation_colmax(source, target):
     B, N, C = source.shape
     out = source.new_empty((B, N))
     with _on_device(source) as stream:
-        _lib.check(_lib.load().ffwm_correlation_colmax(_ptr(source), _ptr(target), _ptr(out), B, N, C, _lib.F32, stream),
-                   "ffwm_correlation_colmax")
+        entry = "ffwm_correlation_colmax_split" if precision == "bf16x3" else "ffwm_correlation_colmax"
+        _lib.check(getattr(_lib.load(), entry)(_ptr(source), _ptr(target), _ptr(out), B, N, C, _lib.F32, stream), entry)
     return out
 
 

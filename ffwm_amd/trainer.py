@@ -1094,7 +1094,7 @@ class FlowNetTrainer(object):
     affine-regularisation kernel.  VGG19 is seeded random (no pretrained weights offline), frozen."""
 
     def __init__(self, device, world_size=1, seed=0, ngf=64, warp=None, fused_regularization=None, bucket_bytes=64 << 20,
-                 routed=None, capturable=False, fused_correctness=False):
+                 routed=None, capturable=False, fused_correctness=False, corr_precision="fp32"):
         from .losses import MultiAffineRegularizationLoss, MultiScaleLDLoss, PerceptualCorrectness
         self.device = torch.device(device)
         torch.manual_seed(seed)
@@ -1116,7 +1116,9 @@ class FlowNetTrainer(object):
         self.Regularization = MultiAffineRegularizationLoss({1: 7, 2: 5, 3: 3}, fused=fused_regularization)
         # fused_correctness: each scale of the correctness loss as one kernel (csrc/sampling_correctness.hip) instead of the warp +
         # cosine + exp composition; off by default
-        self.Correctness = PerceptualCorrectness(self.vgg, self.warp, fused=bool(fused_correctness) and self.device.type == "cuda")
+        # corr_precision: "bf16x3" takes the correlation maximum of that loss on the bf16 MFMA kernel (csrc/correlation.hip); fp32 by default
+        self.Correctness = PerceptualCorrectness(self.vgg, self.warp, fused=bool(fused_correctness) and self.device.type == "cuda",
+                                                 corr_precision=corr_precision)
         self.criterionLD = MultiScaleLDLoss()
         # the same routes FFWMTrainer gives its flow nets (round 3): Winograd forward / data gradient, conv_fwd.hip for the stride-2 /
         # transposed / small-plane layers, direct kernels for the two-channel layers, tiled weight gradients, fused BatchNorm + LeakyReLU

@@ -18,6 +18,7 @@
  *   ffwm_guided_filter_*            <- GuidedFilter.forward             models/external_function.py:239-277
  *   ffwm_affine_regularization      <- AffineRegularizationLoss.__call__ models/losses.py:200-219
  *   ffwm_correlation_colmax         <- max(bmm(source, target), dim=1)  models/losses.py:347-353
+ *   ffwm_correlation_colmax_split   <- the same on bf16 MFMA with a hi/lo operand split (opt-in)
  *   ffwm_sampling_correctness       <- PerceptualCorrectness.calculate_loss (warp, cosine, exp, mask, sums)  models/losses.py:341-371
  *   ffwm_block_attention_*          <- avg_pool2d(BlockExtractor * LocalAttnReshape)  (composition of the ops above)
  *   ffwm_spectral_norm_*            <- torch.nn.utils.spectral_norm hooks models/base_networks.py:5,218-264,381-413
@@ -302,6 +303,18 @@ int ffwm_affine_regularization(const void* flow, const void* ktk, void* loss_sum
  * source[B,N,C], target[B,C,N] contiguous float32, C in {64, 128, 256}, out[B,N]. */
 int ffwm_correlation_colmax(const void* source, const void* target, void* out, int64_t B, int64_t N,
                             int64_t C, int dtype, void* stream);
+
+/* The same maximum on the bf16 matrix instruction (v_mfma_f32_32x32x16_bf16, 16 x the fp32 MFMA rate), opt-in.  Every operand
+ * element is split as hi = bf16_rn(x), lo = bf16_rn(x - hi); a product sum is lo.hi + hi.lo + hi.hi in one fp32 accumulator (lo.lo
+ * dropped): three MFMAs per 16 k.  Operands, shapes, size limits, argument checks and error codes are those of
+ * ffwm_correlation_colmax; profiler row `correlation_colmax_split` (the fp32 row's algorithmic bytes and flops).
+ *   |prod_ij - ref_ij| <= (2^-16 + 3 C fp32 roundings) sum_k |s_ik t_kj|   (tests/colmax_split_bounds.py; 1-3e-6 on normalised
+ *   features, the fp32 kernel: C roundings).  No atomics; two calls agree bit for bit.
+ * Non-finite values: a NaN in source row i makes out[b, :] NaN, a NaN in target column j makes out[b, j] NaN alone; an INFINITE
+ * operand has lo = NaN and so behaves as a NaN in its row / column (ffwm_correlation_colmax propagates the infinity instead);
+ * finite |x| >= 2^127 may round to infinity and is outside the contract. */
+int ffwm_correlation_colmax_split(const void* source, const void* target, void* out, int64_t B, int64_t N,
+                                  int64_t C, int dtype, void* stream);
 
 /* ---- fused sampling-correctness loss (FlowNet pre-training) -------------------------------------
  * PerceptualCorrectness.calculate_loss of models/losses.py:341-371 on its bilinear branch (:356-357), for one flow scale, after

@@ -53,6 +53,9 @@ def main():
                     help="warp sampling grid: random = U[-1.1,1.1) per pixel (worst case: every lane its own cache line), "
                          "smooth = identity grid + a few pixels of low-frequency displacement (a trained FlowNet), "
                          "const = every pixel samples the image centre (an untrained FlowNet, tanh(~0))")
+    ap.add_argument("--corr-precision", default="fp32", choices=["fp32", "bf16x3"],
+                    help="correlation maximum of --only corr / correctness: the fp32 MFMA kernel, or the bf16 MFMA kernel on hi/lo-split "
+                         "operands (ops.correlation_colmax(precision=...))")
     args = ap.parse_args()
     for kv in args.opt:
         k, v = kv.split("=")
@@ -174,9 +177,10 @@ def main():
             t_ = torch.randn(6, C, N, generator=g).to(dev)
             s_ = s_ / (s_.norm(dim=2, keepdim=True) + 1e-8)
             t_ = t_ / (t_.norm(dim=1, keepdim=True) + 1e-8)
-            rows = run("correlation colmax B=6 N=%d C=%d" % (N, C), lambda: ops.correlation_colmax(s_, t_), args.reps)
+            rows = run("correlation colmax %s B=6 N=%d C=%d" % (args.corr_precision, N, C),
+                       lambda: ops.correlation_colmax(s_, t_, precision=args.corr_precision), args.reps)
             for r in rows:
-                r["TFLOPs"] = round(2.0 * 6 * N * N * C / (r["avg_ms"] * 1e-3) / 1e12, 1)
+                r["TFLOPs"] = round(2.0 * 6 * N * N * C / (r["avg_ms"] * 1e-3) / 1e12, 1)       # algorithmic flops, either precision
                 r["frac_fp32_mfma_peak"] = round(r["TFLOPs"] / 157.3, 3)
             results += rows
             for _ in range(3):
@@ -226,7 +230,7 @@ def main():
             tgt = (torch.rand(6, C, S, S, generator=g) + 0.1).to(dev)
             fl = make_flow(6, S).requires_grad_(True)
             for fused in (False, True):
-                pc = PerceptualCorrectness(None, WarpNet(), fused=fused)
+                pc = PerceptualCorrectness(None, WarpNet(), fused=fused, corr_precision=args.corr_precision)
                 pc.target_vgg, pc.source_vgg = {"x": tgt}, {"x": src}
 
                 def step():
@@ -240,7 +244,8 @@ def main():
                     step()
                 torch.cuda.synchronize()
                 ms = (time.perf_counter() - t0) / args.reps * 1e3
-                name = "correctness loss fwd+bwd [6,%d,%d,%d] flow=%s, %s" % (C, S, S, args.warp_flow, "fused kernel" if fused else "op composition")
+                name = "correctness loss fwd+bwd [6,%d,%d,%d] flow=%s corr=%s, %s" % (C, S, S, args.warp_flow, args.corr_precision,
+                                                                                     "fused kernel" if fused else "op composition")
                 results.append({"case": name, "kernel": "wall", "avg_ms": round(ms, 4)})
                 rows = run(name, step, args.reps)
                 lib_launches = sum(r.get("launches", 0) for r in rows) / float(args.reps)
