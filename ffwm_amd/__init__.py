@@ -6,5 +6,15 @@ csyxwei/FFWM: hand-written HIP kernels behind the reference's own operator API.
     ffwm_amd.compat              block_extractor_cuda / local_attn_reshape_cuda / resample2d_cuda shims
     ffwm_amd.ops                 tensor-level calls into the C ABI (include/ffwm_hip.h)
     ffwm_amd.build               hipcc build recipe for ffwm_amd/lib/libffwm_hip.so
+    ffwm_amd.Frontalizer         inference as the reference's test_ffwm.py runs it: flowNetF -> WarpNet -> netG from two
+                                 checkpoints, one captured hipGraph (ffwm_amd.ffwm_eval; FoldedFFWM is the generator alone)
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # imported on first use: `import ffwm_amd` stays free of torch
+    if name in ("Frontalizer", "FoldedFFWM", "FrontalizerResult"):
+        from . import ffwm_eval
+        return getattr(ffwm_eval, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -40,6 +40,10 @@ _SIGNATURES = {
     "ffwm_flow_head_forward": [_p, _p, _p, _p] + [_i64] * 4 + [_i, _p],
     "ffwm_conv_thin_forward": [_p, _p, _p, _p] + [_i64] * 5 + [_i, ctypes.c_double, _i, _p],
     "ffwm_flow_up_forward": [_p, _p, _p, _p] + [_i64] * 4 + [_i, _p],
+    "ffwm_shuffle_bias_act_forward": [_p, _p, _p] + [_i64] * 5 + [ctypes.c_double, _i, _p],
+    "ffwm_image_head_forward": [_p, _p, _p, _p] + [_i64] * 5 + [_i, _p],
+    "ffwm_upsample2x_bilinear_forward": [_p, _p] + [_i64] * 5 + [_i, _p],
+    "ffwm_sigmoid_gate_forward_strided": [_p, _p, _p, _p, _p] + [_i64] * 4 + [_i, _p],
     "ffwm_flow_head_backward": [_p, _p, _p, _p, _p] + [_i64] * 4 + [_i, _p],
     "ffwm_flow_up_backward": [_p, _p, _p] + [_i64] * 4 + [_i, _p],
     "ffwm_conv2d_forward": [_p, _p, _p, _p, _p] + [_i64] * 5 + [_i, _i, _i, _i, _i64, _i64, _i, ctypes.c_double, _p, _i64, _i, _p],

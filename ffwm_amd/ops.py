@@ -821,6 +821,79 @@ def sigmoid_gate_backward(x, att, grad_y):
     return dz, dx
 
 
+# ---------------------------------------------------------------- netG eval forward (csrc/netg_eval.hip)
+def _f32_in(name, *ts):
+    t0 = ts[0]
+    for t in ts:
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == t0.device):
+            raise NotImplementedError("%s: contiguous float32 tensors on one GPU only" % name)
+
+
+def _dest_view(name, out, shape, like):
+    """out: None (a fresh contiguous tensor) or a destination view -- [B, C, H, W] of `shape` whose samples are contiguous (a
+    channel slice of a concatenation buffer); -> (tensor, batch stride)."""
+    if out is None:
+        out = like.new_empty(shape)
+    B, C, H, W = shape
+    if not (out.is_cuda and out.dtype == torch.float32 and out.device == like.device and tuple(out.shape) == tuple(shape)
+            and out.stride(3) == 1 and out.stride(2) == W and out.stride(1) == H * W and out.stride(0) >= C * H * W):
+        raise ValueError("%s: the destination must be a float32 [%d, %d, %d, %d] view with contiguous samples" % ((name,) + tuple(shape)))
+    return out, out.stride(0)
+
+
+def shuffle_bias_act(h, bias, slope=0.2, out=None):
+    """lrelu(pixel_shuffle(h, 2) + bias[k]) of h [B, 4K, H, W] (base_networks.py:261-272 with the BatchNorm folded) in one pass,
+    into `out` (a destination view [B, K, 2H, 2W]) or a fresh tensor."""
+    _f32_in("shuffle_bias_act", h, bias)
+    B, C4, H, W = h.shape
+    if C4 % 4 or (bias is not None and bias.numel() != C4 // 4):
+        raise ValueError("shuffle_bias_act: h must have 4K channels and bias K elements")
+    K = C4 // 4
+    out, obs = _dest_view("shuffle_bias_act", out, (B, K, 2 * H, 2 * W), h)
+    with _on_device(h) as stream:
+        _lib.check(_lib.load().ffwm_shuffle_bias_act_forward(_ptr(h), _ptr(bias), _ptr(out), B, K, H, W, obs, float(slope), _lib.F32, stream),
+                   "ffwm_shuffle_bias_act_forward")
+    return out
+
+
+def image_head(x, weight, bias, out=None):
+    """sigmoid(conv2d(x, weight [3, C, 3, 3], bias, stride 1, padding 1)): netG's rec0 / rec1 / rec2 as one direct kernel."""
+    _f32_in("image_head", x, weight, bias)
+    B, C, H, W = x.shape
+    if tuple(weight.shape) != (3, C, 3, 3) or (bias is not None and bias.numel() != 3):
+        raise ValueError("image_head: weight [3, %d, 3, 3] and bias [3] expected" % C)
+    out, obs = _dest_view("image_head", out, (B, 3, H, W), x)
+    with _on_device(x) as stream:
+        _lib.check(_lib.load().ffwm_image_head_forward(_ptr(x), _ptr(weight), _ptr(bias), _ptr(out), B, C, H, W, obs, _lib.F32, stream),
+                   "ffwm_image_head_forward")
+    return out
+
+
+def upsample2x_bilinear(x, out=None):
+    """F.interpolate(x, scale_factor=2, mode="bilinear") (align_corners=False) into `out` (a destination view) or a fresh tensor."""
+    _f32_in("upsample2x_bilinear", x)
+    B, C, H, W = x.shape
+    out, obs = _dest_view("upsample2x_bilinear", out, (B, C, 2 * H, 2 * W), x)
+    with _on_device(x) as stream:
+        _lib.check(_lib.load().ffwm_upsample2x_bilinear_forward(_ptr(x), _ptr(out), B, C, H, W, obs, _lib.F32, stream),
+                   "ffwm_upsample2x_bilinear_forward")
+    return out
+
+
+def sigmoid_gate_forward_strided(a, b, x, out=None, want_att=True):
+    """-> (y, att or None): sigmoid_gate_forward with y written into `out` (a destination view); want_att=False skips att."""
+    _same_f32("sigmoid_gate_forward_strided", a, b, x)
+    if a.dim() != 4:
+        raise ValueError("sigmoid_gate_forward_strided: 4-D tensors expected")
+    B, C, H, W = a.shape
+    out, obs = _dest_view("sigmoid_gate_forward_strided", out, (B, C, H, W), a)
+    att = torch.empty_like(a) if want_att else None
+    with _on_device(a) as stream:
+        _lib.check(_lib.load().ffwm_sigmoid_gate_forward_strided(_ptr(a), _ptr(b), _ptr(x), _ptr(att), _ptr(out), B, C, H * W, obs, _lib.F32,
+                                                                 stream), "ffwm_sigmoid_gate_forward_strided")
+    return out, att
+
+
 def mfm_forward(x, bias=None):
     """max(x[:, :C] + bias[:C], x[:, C:] + bias[C:]) of a contiguous float32 [B, 2C, ...] tensor."""
     if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()):

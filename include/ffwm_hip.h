@@ -569,6 +569,34 @@ int ffwm_adam_step(void* params, const void* grads, void* exp_avg, void* exp_avg
 int ffwm_adam_step_device(void* params, const void* grads, void* exp_avg, void* exp_avg_sq, int64_t n, double lr, double beta1,
                           double beta2, double eps, void* state, int dtype, void* stream);
 
+/* ---- netG eval forward (models/base_networks.py:274-347): the layers around the dense convolutions once BatchNorm is folded
+ * into the conv weights (ffwm_amd/ffwm_eval.py, csrc/netg_eval.hip).  float32, forward only.
+ *
+ * A DESTINATION VIEW is a [B, C, H, W] view whose samples are contiguous: sample b starts at y + b * y_batch_stride.  A channel
+ * slice of the decoder's concatenation buffer is one, so cat(skip * att, dec, up(recon)) (:334-340) is written in place by the
+ * three producers and never copied.  Every entry point returns FFWM_ERR_DTYPE for a dtype other than FFWM_F32, FFWM_ERR_ARG for
+ * a NULL tensor pointer, a non-positive size or a batch stride smaller than one sample of the view, FFWM_ERR_SIZE for a plane
+ * past its index range -- all before any launch.
+ *
+ * ffwm_shuffle_bias_act_forward: PixelShuffle(2) -> per-channel shift -> LeakyReLU of a decoder block (:261-272) in one pass:
+ *   y[b, k, 2 yy + i, 2 xx + j] = lrelu(h[b, 4 k + 2 i + j, yy, xx] + bias[k]),  h [B, 4 K, H, W] contiguous, bias [K] or NULL,
+ *   y a destination view [B, K, 2 H, 2 W].
+ * ffwm_image_head_forward: y = sigmoid(conv2d(x[B, C, H, W], weight[3, C, 3, 3], stride 1, pad 1) + bias[3]) (rec0 / rec1 / rec2,
+ *   :303-305) by a direct kernel staged through LDS, any H and W; y a destination view [B, 3, H, W].  Partial sums meet in a fixed
+ *   order: bit-reproducible.
+ * ffwm_upsample2x_bilinear_forward: F.interpolate(x[B, C, H, W], scale_factor=2, mode="bilinear") with align_corners=False (:337)
+ *   into a destination view [B, C, 2 H, 2 W].
+ * ffwm_sigmoid_gate_forward_strided: ffwm_sigmoid_gate_forward (same arithmetic, same order) on [B, C, HW] tensors with y in a
+ *   destination view; att (contiguous) may be NULL: not written. */
+int ffwm_shuffle_bias_act_forward(const void* h, const void* bias, void* y, int64_t B, int64_t K, int64_t H, int64_t W,
+                                  int64_t y_batch_stride, double negative_slope, int dtype, void* stream);
+int ffwm_image_head_forward(const void* x, const void* weight, const void* bias, void* y, int64_t B, int64_t C, int64_t H, int64_t W,
+                            int64_t y_batch_stride, int dtype, void* stream);
+int ffwm_upsample2x_bilinear_forward(const void* x, void* y, int64_t B, int64_t C, int64_t H, int64_t W, int64_t y_batch_stride,
+                                     int dtype, void* stream);
+int ffwm_sigmoid_gate_forward_strided(const void* a, const void* b, const void* x, void* att, void* y, int64_t B, int64_t C,
+                                      int64_t HW, int64_t y_batch_stride, int dtype, void* stream);
+
 /* ---- built-in per-kernel timing (HIP events on the launch stream) ---------------------------
  * ffwm_prof_enable(1) brackets every kernel launch of this library with a pair of HIP events
  * recorded on the stream the kernel is launched on.  ffwm_prof_collect() waits for the recorded

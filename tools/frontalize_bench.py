@@ -1,0 +1,162 @@
+"""Inference as the reference's test_ffwm.py runs it (flowNetF -> WarpNet -> netG, 128 x 128), two ways in ONE process, alternating:
+
+    python tools/frontalize_bench.py [--reps 5] [--seconds 0.5] [--out profiles/frontalizer.txt]
+
+(A) what the library offered before ffwm_amd/ffwm_eval.py: FoldedFlowNet(graph=True) + the HIP warp + nets.FFWM with
+    conv.route_training_kernels applied, eval mode under no_grad, eager;
+(B) ffwm_amd.Frontalizer: folded netG, the flow net and the warp in one captured hipGraph.
+
+Both from the same weights (tests/golden/fill.py: a default-initialised netG overflows in eval mode), batch 1 and batch 8.  Every shape
+is warmed first; a leg is timed with device events around as many calls as fill --seconds; the legs alternate A / B / A / B and each
+is reported as median and min-max over --reps repetitions.  End-to-end forward times, not a share of any peak.  The kernel launches
+of one forward: B from Frontalizer.plan() (netG) plus FoldedFlowNet's and the warp's, A by the profiler's kernel events of one call
+(taken last, outside the timed legs).  GPU only: without a device the tool fails.
+"""
+import argparse
+import copy
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+import torch  # noqa: E402
+
+import fill  # noqa: E402
+
+DEV = "cuda:0"
+
+
+def time_leg(fn, seconds):
+    """ms per call: device events around n back-to-back calls, n sized from a short probe so that the window lasts `seconds`."""
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(5):
+        fn()
+    stop.record()
+    stop.synchronize()
+    per = max(start.elapsed_time(stop) / 5, 1e-3)
+    n = max(5, int(seconds * 1e3 / per) + 1)
+    start.record()
+    for _ in range(n):
+        fn()
+    stop.record()
+    stop.synchronize()
+    return start.elapsed_time(stop) / n, n
+
+
+def kernel_events(fn):
+    """Device kernel launches of one call, counted by the profiler; None when it cannot be had."""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        fn()
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        n = 0
+        for e in prof.events():
+            if str(getattr(e, "device_type", "")).endswith("CUDA") and "memcpy" not in e.name.lower() and "memset" not in e.name.lower():
+                n += 1
+        return n or None
+    except Exception as exc:          # the count is a side note: the timings above stand without it
+        sys.stderr.write("kernel count not available: %r\n" % (exc,))
+        return None
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--seconds", type=float, default=0.5, help="length of one timed window")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "frontalizer.txt"))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("frontalize_bench: needs an MI355X; a CPU run measures nothing")
+
+    from ffwm_amd import Frontalizer, conv, nets
+    from ffwm_amd.external_function import WarpNet
+    from ffwm_amd.flownet_eval import FoldedFlowNet
+
+    lines = []
+
+    def out(s=""):
+        print(s, flush=True)
+        lines.append(s)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+    flowNetF = fill.fill_module(nets.FlowNet(64)).to(DEV).eval()
+    netG = fill.fill_module(nets.FFWM(sn=True)).to(DEV).eval()
+    fill.boost_output_gain(netG)
+    frontalizer = Frontalizer(flowNetF, copy.deepcopy(netG), graph=True)
+    routed = conv.route_training_kernels(netG)
+    netG.eval()
+    flow_a, warp_a = FoldedFlowNet(flowNetF, graph=True), WarpNet()
+
+    @torch.no_grad()
+    def leg_a(img):
+        f128, f64, f32 = flow_a(img)
+        warped = warp_a(img, f128)
+        _, _, fake, att = netG(img, flow=[f32, f64, f128], return_att=True)
+        return fake, warped, torch.mean(att[:, :64], (1,), keepdim=True)
+
+    def leg_b(img):
+        r = frontalizer(img)
+        return r.fake_F128, r.img_S_warp, r.att
+
+    out("# frontalizer: flowNetF -> WarpNet -> netG at 128 x 128, float32, device %s" % torch.cuda.get_device_name(0))
+    out("# A = FoldedFlowNet(graph) + HIP warp + nets.FFWM with route_training_kernels %s, eval, no_grad, eager" % (routed,))
+    out("# B = Frontalizer(graph=True): folded netG + flow net + warp in one captured hipGraph")
+    out("# per leg: ms per forward from device events over a window of >= %.2f s; %d repetitions, alternating A / B" % (args.seconds, args.reps))
+    imgs = {B: fill.image(B, 3, 128, 128, "eval_img_S").to(DEV) for B in (1, 8)}
+    kept = {}
+    for B, img in imgs.items():          # warm every shape of both legs (solver selection, kept Winograd transforms, the captures)
+        for _ in range(3):
+            a, b = leg_a(img), leg_b(img)
+        torch.cuda.synchronize()
+        diff = max((x - y).abs().max().item() for x, y in zip(a, b))
+        out("batch %d: max |A - B| over fake_F128, img_S_warp, att = %.3e" % (B, diff))
+        kept[B] = [t.clone() for t in b]
+    verdicts = {}
+    for B, img in imgs.items():
+        ms = {"A": [], "B": []}
+        calls = {}
+        leg_b(img)                        # the capture of this shape (a shape change re-captures)
+        torch.cuda.synchronize()
+        for _ in range(args.reps):
+            for name, fn in (("A", leg_a), ("B", leg_b)):
+                t, n = time_leg(lambda: fn(img), args.seconds)
+                ms[name].append(t)
+                calls[name] = n
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        spread = {k: max(v) - min(v) for k, v in ms.items()}
+        for k in ("A", "B"):
+            out("batch %d  %s  median %.3f ms  min %.3f  max %.3f  (%d calls per window)  runs [%s]"
+                % (B, k, med[k], min(ms[k]), max(ms[k]), calls[k], ", ".join("%.3f" % x for x in ms[k])))
+        drift = max((x - y).abs().max().item() for x, y in zip(leg_b(img), kept[B]))
+        out("batch %d  B after the timed legs against B before them: max abs diff %.3e" % (B, drift))
+        margin, worst = med["A"] - med["B"], max(spread.values())
+        verdicts[B] = (margin, worst)
+        out("batch %d  A - B = %.3f ms against the larger min-max spread %.3f ms: %s; A / B = %.2f"
+            % (B, margin, worst, "B is faster beyond the spread" if margin > worst else
+               ("B is not slower beyond the spread" if margin >= -worst else "B is SLOWER beyond the spread"), med["A"] / med["B"]))
+    out("# pass conditions: batch 1 needs A - B > spread: %s; batch 8 needs A - B >= -spread: %s"
+        % ("met" if verdicts[1][0] > verdicts[1][1] else "MISSED", "met" if verdicts[8][0] >= -verdicts[8][1] else "MISSED"))
+    for B in (1, 8):
+        plan = frontalizer.plan(B, 128, 128)
+        kinds = {}
+        for _, k in plan:
+            kinds[k] = kinds.get(k, 0) + 1
+        out("batch %d  B netG launches from plan(): %d  %s (inside one graph launch, with FoldedFlowNet's and the image warp's)"
+            % (B, len(plan), ", ".join("%s %d" % kv for kv in sorted(kinds.items()))))
+    for B, img in imgs.items():
+        n_a = kernel_events(lambda: leg_a(img))
+        n_b = kernel_events(lambda: leg_b(img))
+        out("batch %d  kernel events of one forward (profiler): A %s (its flow net replays from a graph), B %s"
+            % (B, n_a if n_a is not None else "not measured", n_b if n_b is not None else "not measured"))
+
+
+if __name__ == "__main__":
+    main()
