@@ -15,6 +15,11 @@
 namespace ffwm {
 namespace {
 
+// ATen's NaN rule, which fmaxf alone does not follow (it returns the non-NaN operand): maximum(a, b) is NaN when either operand
+// is, relu(NaN) is NaN.  Every other value is fmaxf's.
+__device__ __forceinline__ float max_nan(float a, float b) { return __builtin_isunordered(a, b) ? a + b : fmaxf(a, b); }
+__device__ __forceinline__ float relu_nan(float v) { return v != v ? v : fmaxf(v, 0.f); }
+
 // n4 = float4 per (b, c) row; rows = B * C; the partner row is C rows further inside the same sample
 __global__ void __launch_bounds__(kBlock)
 mfm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ bias, float* __restrict__ y, int64_t total, int C, int HW) {
@@ -24,7 +29,7 @@ mfm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ bias, floa
         const float* p = x + b * 2 * half + r;
         const int c = static_cast<int>(r / HW);
         const float ba = bias ? bias[c] : 0.f, bb = bias ? bias[C + c] : 0.f;
-        y[i] = fmaxf(p[0] + ba, p[half] + bb);
+        y[i] = max_nan(p[0] + ba, p[half] + bb);
     }
 }
 
@@ -36,7 +41,7 @@ mfm_fwd4_kernel(const float4* __restrict__ x, const float* __restrict__ bias, fl
         const float4 a = x[b * 2 * half4 + r], c = x[b * 2 * half4 + half4 + r];
         const int ch = static_cast<int>(r / HW4);
         const float ba = bias ? bias[ch] : 0.f, bb = bias ? bias[C + ch] : 0.f;
-        y[i] = float4{fmaxf(a.x + ba, c.x + bb), fmaxf(a.y + ba, c.y + bb), fmaxf(a.z + ba, c.z + bb), fmaxf(a.w + ba, c.w + bb)};
+        y[i] = float4{max_nan(a.x + ba, c.x + bb), max_nan(a.y + ba, c.y + bb), max_nan(a.z + ba, c.z + bb), max_nan(a.w + ba, c.w + bb)};
     }
 }
 
@@ -86,7 +91,7 @@ __global__ void __launch_bounds__(kBlock)
 bias_relu_kernel(const float* __restrict__ h, const float* __restrict__ bias, float* __restrict__ y, int64_t total, int C, int HW) {
     for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < total; i += static_cast<int64_t>(gridDim.x) * kBlock) {
         const int c = static_cast<int>((i / HW) % C);
-        y[i] = fmaxf(h[i] + bias[c], 0.f);
+        y[i] = relu_nan(h[i] + bias[c]);
     }
 }
 
@@ -95,7 +100,7 @@ bias_relu4_kernel(const float4* __restrict__ h, const float* __restrict__ bias, 
     for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < total4; i += static_cast<int64_t>(gridDim.x) * kBlock) {
         const float bc = bias[static_cast<int>((i / HW4) % C)];
         const float4 v = h[i];
-        y[i] = float4{fmaxf(v.x + bc, 0.f), fmaxf(v.y + bc, 0.f), fmaxf(v.z + bc, 0.f), fmaxf(v.w + bc, 0.f)};
+        y[i] = float4{relu_nan(v.x + bc), relu_nan(v.y + bc), relu_nan(v.z + bc), relu_nan(v.w + bc)};
     }
 }
 

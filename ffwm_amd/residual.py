@@ -24,7 +24,7 @@ class _AddAct(Function):
     @once_differentiable
     def backward(ctx, g):
         (y,) = ctx.saved_tensors
-        dz = ops.add_act_backward(y, g.contiguous(), ctx.act, ctx.slope)
+        dz = ops.add_act_backward(y, _grad_in(g), ctx.act, ctx.slope)
         return dz, dz, None, None
 
 
@@ -41,7 +41,7 @@ class _SigmoidGate(Function):
     @once_differentiable
     def backward(ctx, gy, _gatt):
         x, att = ctx.saved_tensors
-        dz, dx = ops.sigmoid_gate_backward(x, att, gy.contiguous())
+        dz, dx = ops.sigmoid_gate_backward(x, att, _grad_in(gy))
         return dz, dz, dx
 
 
@@ -53,10 +53,22 @@ def _act_of(module):
     return None, 0.0
 
 
+def _aligned(t):
+    """What .contiguous() hands the kernel starts on a 16-byte boundary (residual.hip requires it): a fresh copy always does, a
+    contiguous view at an odd element offset of its buffer does not."""
+    return not t.is_contiguous() or t.data_ptr() % 16 == 0
+
+
 def _kernel_ok(*ts):
     t0 = ts[0]
     return (t0.is_cuda and not torch.is_autocast_enabled()
-            and all(t.dtype == torch.float32 and t.shape == t0.shape and t.device == t0.device for t in ts))
+            and all(t.dtype == torch.float32 and t.shape == t0.shape and t.device == t0.device and _aligned(t) for t in ts))
+
+
+def _grad_in(g):
+    """The incoming gradient as the kernel takes it: contiguous, and copied when it is a misaligned view."""
+    g = g.contiguous()
+    return g if g.data_ptr() % 16 == 0 else g.clone()
 
 
 def add_act(a, b, activ):

@@ -414,11 +414,13 @@ def test_conv2d_wgrad_generic_per_element(name, kind):
 
 
 # ------------------------------------------------------------------------------------------------ the thin kernels of flownet_ops.hip
-FLOW_HEADS = [(8, 1024, 2, 2), (8, 256, 8, 8), (3, 70, 9, 11), (8, 32, 64, 64), (2, 16, 128, 128)]
+# (the last two resolve to 16 pixels per block -- the second ends in a partial tile --, the others to 4 or 64: flow_head_tile as
+# tests/small_kernel_bounds.py restates it)
+FLOW_HEADS = [(8, 1024, 2, 2), (8, 256, 8, 8), (3, 70, 9, 11), (8, 32, 64, 64), (2, 16, 128, 128), (6, 128, 16, 16), (4, 70, 19, 23)]
 
 
 @pytest.mark.parametrize("shape,kind", [pytest.param(s, k, id="%dx%dx%dx%d-%s" % (s + (k,))) for s in FLOW_HEADS
-                                        for k in _kinds(s in ((3, 70, 9, 11), (8, 32, 64, 64)))])
+                                        for k in _kinds(s in ((3, 70, 9, 11), (8, 32, 64, 64), (4, 70, 19, 23)))])
 def test_flow_head_per_element(shape, kind):
     """Conv2d(C, 2, 3, 1, 1) + bias + tanh in one launch.  Integers: the pre-activation is exact, so the result is within the 4 ulps
     of tanhf alone (rho = 0)."""

@@ -41,7 +41,9 @@ def _guarded(B, C, H, W, before=2, after=3):
 
 
 # ---------------------------------------------------------------------------------------------------- the four kernels
-@pytest.mark.parametrize("shape", [(2, 3, 5, 7), (1, 64, 16, 16)])
+# the last two pass one sweep of the 2048-block grid (524 288 threads) on the vector and on the scalar route: h is [1, 132, 256, 256]
+# and [1, 36, 241, 243]
+@pytest.mark.parametrize("shape", [(2, 3, 5, 7), (1, 64, 16, 16), (1, 33, 256, 256), (1, 9, 241, 243)])
 def test_shuffle_bias_act(shape):
     """One add and one multiply per element, nothing to reassociate: equal to the PyTorch composition bit for bit."""
     from ffwm_amd import ops
@@ -58,7 +60,8 @@ def test_shuffle_bias_act(shape):
     assert torch.equal(ops.shuffle_bias_act(h, bias, 0.2), ref)          # a fresh contiguous destination
 
 
-@pytest.mark.parametrize("shape", [(2, 3, 1, 1), (1, 3, 5, 7), (2, 3, 32, 32)])
+# (the last two: past 524 288 threads, four output pixels per lane and one)
+@pytest.mark.parametrize("shape", [(2, 3, 1, 1), (1, 3, 5, 7), (2, 3, 32, 32), (1, 3, 512, 360), (1, 3, 211, 209)])
 def test_upsample2x_bilinear(shape):
     """A four-term combination whose weights and weight products (0.25, 0.75, 0.0625, 0.1875, 0.5625) are exact:
     <= 4 eps32 max|x| against float64 F.interpolate."""

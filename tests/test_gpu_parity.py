@@ -2416,7 +2416,7 @@ def test_l1_terms_match_torch_forward_and_backward():
 
 
 # ------------------------------------------------------------------------------------------------ FlowNet's two-channel layers in training
-@pytest.mark.parametrize("case", [(8, 1024, 2, 2), (8, 256, 8, 8), (3, 70, 9, 11), (8, 32, 64, 64), (2, 16, 128, 128)])
+@pytest.mark.parametrize("case", [(8, 1024, 2, 2), (8, 256, 8, 8), (3, 70, 9, 11), (8, 32, 64, 64), (2, 16, 128, 128), (6, 128, 16, 16)])
 def test_flow_head_training_route_matches_torch(case):
     """conv.FlowHead (Conv2d(C, 2, 3, 1, 1) + Tanh on csrc/flownet_ops.hip forward and backward, weight gradient on the tiled kernel)
     against the nn.Sequential it re-classes (base_networks.py:45-49): output, d(input), d(weight), d(bias) in float64."""
