@@ -1104,7 +1104,7 @@ template <int K, int RH, int H, bool FIXED = false>          // FIXED: fixed-poi
 __global__ void __launch_bounds__(kBlock, (RH == 32 && K <= 3 && H <= 4 ? 4 : 2))
 be_bwd_tile2_kernel(const float* __restrict__ src, const float* __restrict__ flow, const float* __restrict__ gout,
                    float* __restrict__ gsrc, float* __restrict__ gflow, int C, int Hs, int Ws, int Hf, int Wf,
-                   int ntx, int nty, int cslabs, int cs, int remap, int flush_rmw = 0) {
+                   int ntx, int nty, int cslabs, int cs, int remap, int flush_rmw) {
     using T = float;
     constexpr int RW = kTileRW, NW = kBlock / kWave, PPT = RH / NW;
     constexpr int TW = RW, TH = RH;                       // the block's flow pixels: no overlap with its neighbours
@@ -1545,12 +1545,10 @@ be_bwd_tile2_kernel(const float* __restrict__ src, const float* __restrict__ flo
             // flush + restage in one sweep over the box: one global atomic per non-zero in-image cell of
             // channel c (then the cell is cleared), and the same cell of channel c+1's clamp-extended
             // source goes into S -- an in-image cell has the same plane offset in both.
-            // Round 6 experiment (flush_rmw, option be_bwd_flush = 1, OFF): the INTERIOR cells -- box columns [2H, TW) x rows [2H, TH), i.e.
-            // the tile shrunk by H: no other block's box reaches them, the far kernel's atomics are a finished earlier launch -- added by a
-            // plain read-modify-write, with ALL old values of a thread's cells requested up front through L2 (sc0 sc1).  Measured on one
-            // box, cfg-5 (profiles/r06_be_flush_rmw_negative.txt): 432 -> 577 us random, 414 -> 565 us smooth; block attention 401 -> 538.
-            // Like round 4's attempt (loads issued where needed: 597 -> 679): a return-less atomic is ONE write transaction resolved at
-            // L2, the read-modify-write a round trip per cell that the four resident blocks do not cover.  The atomics stay.
+            // flush_rmw (always 0: every launch passes the constant, no option reaches it) is round 6's experiment, interior cells by
+            // read-modify-write: slower, profiles/r06_be_flush_rmw_negative.txt.  Its arm stays in the text because the kernel WITHOUT it,
+            // with 850 instructions fewer and the same registers, came out 2-3 % slower on cfg-5 in 11 of 11 alternating pairs
+            // (profiles/prune_untested_switches_parent_vs_after.txt): hipcc allocates and schedules the whole kernel differently.
             T* gplane = gp + static_cast<size_t>(c - c0) * splane;
             const rsrc_t rn = make_rsrc(sp + static_cast<size_t>(more ? c + 1 - c0 : c - c0) * splane, more ? sbytes : 0u);
             const rsrc_t rq = make_rsrc(gplane, sbytes);
@@ -1827,11 +1825,11 @@ int launch_fwd(const T* src, const T* flow, T* out, int64_t B, int64_t C, int64_
     const bool lds = !generic && k <= 4 && (variant == 2 || variant == 0);
     bool ok = true;          // false: a dispatch below found no kernel for its value
     if (lds) {
-        // pixel rows per thread: 4 / 2 / 1 (float64: always 1)
-        const int want = sizeof(T) == 8 ? 1 : (options().rows_per_thread > 0 ? options().rows_per_thread : (Hf >= 64 ? 4 : 1));
+        // pixel rows per thread: 4 for planes of >= 64 rows, else 1 (float64: always 1)
+        const int rpt = sizeof(T) == 4 && Hf >= 64 ? 4 : 1;
         LaunchScope ls("block_extractor_fwd_lds", st, bytes);
         ok &= dispatch<1, 2, 3, 4>(k, [&](auto K) {
-            return dispatch<4, 2, 1>(want >= 4 ? 4 : (want >= 2 ? 2 : 1), [&](auto RPT) {
+            return dispatch<4, 1>(rpt, [&](auto RPT) {
                 constexpr int TH = (kBlock / kWave) * RPT.value;
                 const int tyl = static_cast<int>((Hf + TH - 1) / TH);
                 const unsigned gridl = static_cast<unsigned>(B * g.tiles_x * tyl * g.cslabs);
@@ -1930,9 +1928,7 @@ int launch_bwd(const T* src, const T* flow, const T* gout, T* gsrc, T* gflow, in
                 constexpr TileGeo geo = Cfg::geo();
                 const int ntx = static_cast<int>(((Ws > Wf ? Ws : Wf) + geo.TW - 1) / geo.TW);
                 const int nty = static_cast<int>(((Hs > Hf ? Hs : Hf) + geo.TH - 1) / geo.TH);
-                int cs = options().channel_slab > 0 ? options().channel_slab : 4;
-                if (cs > C) cs = static_cast<int>(C);
-                cs = halve_slab(cs, C, B * ntx * nty, 1536, 4);   // >= 6 blocks per CU
+                const int cs = C < 4 ? static_cast<int>(C) : 4;
                 const int cslabs = static_cast<int>((C + cs - 1) / cs);
                 const Geometry gf = plan(B, C, Hf, Wf, 32);
                 {
@@ -1953,11 +1949,9 @@ int launch_bwd(const T* src, const T* flow, const T* gout, T* gsrc, T* gflow, in
                 const unsigned grid = static_cast<unsigned>(B * ntx * nty * cslabs);
                 auto launch_k = [&](auto K) {
                     if constexpr (Cfg::SHARED) {
-                        // 1 = interior cells by read-modify-write (round 6 experiment: SLOWER, profiles/r06_be_flush_rmw_negative.txt); 0 = every cell by a global atomic
-                        const int flush_rmw = options().be_bwd_flush == 1 ? 1 : 0;
                         hipLaunchKernelGGL((be_bwd_tile2_kernel<K.value, Cfg::RH, Cfg::HALO, Cfg::FIXED>), dim3(grid), dim3(kBlock), 0, st, (const float*)src,
                                            (const float*)flow, (const float*)gout, (float*)gsrc, (float*)gflow, (int)C, (int)Hs, (int)Ws, (int)Hf,
-                                           (int)Wf, ntx, nty, cslabs, cs, remap, flush_rmw);
+                                           (int)Wf, ntx, nty, cslabs, cs, remap, 0);
                     } else {
                         hipLaunchKernelGGL((be_bwd_tile_kernel<K.value, Cfg::RH, Cfg::HALO>), dim3(grid), dim3(kBlock), 0, st, (const float*)src,
                                            (const float*)flow, (const float*)gout, (float*)gsrc, (float*)gflow, (int)C, (int)Hs, (int)Ws, (int)Hf,

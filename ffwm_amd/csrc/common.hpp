@@ -38,43 +38,28 @@ constexpr int kMaxLdsBytes = 160 * 1024;
 #define FFWM_OPTIONS(X) \
     X(be_fwd_variant, 0)  /* 0 = auto */ \
     X(be_bwd_variant, 0) \
-    X(channel_slab, 0)  /* 0 = auto */ \
     X(xcd_remap, 1) \
     X(scatter_variant, 0)  /* backward scatters: 0 = auto (LDS-resident plane when it fits), 1 = global atomics */ \
-    X(rows_per_thread, 0)  /* block_extractor LDS kernels: 0 = auto, 1 / 2 / 4 */ \
     X(warp_fwd_variant, 0)  /* warp forward: 0 = auto, 1 = direct gathers, 2 = LDS-staged tiles */ \
     X(be_bwd_halo, 0)  /* block_extractor owned-tile backward: halo in pixels (<= 4 -> 4 (default), else 8) */ \
     X(be_bwd_rows, 0)  /* ... region height: 32 (default) or 64 rows */ \
-    X(rs_fwd_variant, 0)  /* resample2d forward: 0 = auto, 1 = direct gathers, LDS-staged tiles 64 x 16 / 4 / 8: 2 / 3 / 4 (two buffers), 6 / 7 / 5 (one) */ \
     X(rs_bwd1_variant, 0)  /* resample2d d_input1: 0 = auto (ks 4: tap-lane kernel, on calls of >= 2^18 pixels the tile kernel instead when a pre-pass finds the flow smooth; else plane kernel when a plane fits LDS, else tile kernel), 1 = round-2 auto (plane / tile), 2 = tile kernel, 5 = tap-lane kernel with 8-wave blocks (16-row tiles) */ \
     X(conv_tile_variant, 0)  /* conv_fwd.hip workgroup tile: 0 auto, 1 = 64 x 64, 2 = 128 x 64, 3 = 64 x 128, 4 = 128 x 128 */ \
     X(conv_wino_raw, 1)  /* conv_winograd.hip: stage the input window through LDS when a workgroup covers whole tile rows */ \
     X(conv_fwd_split_target, 0)  /* conv_fwd.hip: workgroups a launch with < 256 tiles is cut into along the reduction (each slice adds its tile by atomics); 0 = by shape (768 / 384) */ \
-    X(conv_wgrad_slice_target, 0)  /* conv_bwd.hip tiled weight gradient: workgroups a launch is cut into along the pixels (0 = 512) */ \
     X(conv_wino_ws, 0)  /* conv_winograd.hip: the wave-specialised variant (8 MFMA waves + 4 staging waves) for calls without a split reduction */ \
     X(conv_wino_split, 1)  /* conv_winograd.hip: cut the reduction of a call with few (strip, k tile) pairs over 2 / 4 workgroups (atomics into a zeroed output); 2 = at most two pieces (a two-term float sum does not depend on the order: bit-reproducible); 0 = never */ \
     X(conv_thin_tail, 1)  /* conv_winograd.hip: 1-4 output channels past a multiple of 64 on the thin direct kernel */ \
-    X(warp_nt, 0)  /* warp forward (direct / multi-problem kernels): 1 = streaming (nt) stores, 2 = nt feature loads too */ \
-    X(warp_pair_loads, 1)  /* warp d(flow), multi-problem launch, fp32: one 8-byte load per corner ROW instead of two dword gathers */ \
     X(conv_wgrad_wino, 0)  /* conv_wgrad.hip, the full 64-channel tiles on the Winograd-domain kernel (conv_wgrad_wino.hip): 0 = auto (>= 16 chunks per CU), 1 = whenever served, 2 = never */ \
     X(warp_multi_planes, 0)  /* multi-problem warp backward: 0 = d(feat) plane problems of one CG share a launch, 1 = one launch per problem */ \
-    X(warp_multi_lds, 0)  /* multi-problem warp launches: 0 = auto (LDS-staged tiles for float planes >= 64 x 64, C >= 32), 1 = direct gathers, 2 = LDS tiles */ \
-    X(warp_multi_order, 0)  /* multi-problem warp launches: 0 = largest problem first, 1 = the caller's order */ \
-    X(conv_fwd_kfast, 1)  /* conv_fwd.hip: workgroup index with the channel tiles fastest + XCD remap (round 5); 0 = pixel tiles fastest */ \
-    X(warp_feat_gps, 0)  /* warp d(feat) owned-tile kernel: channel groups per block, 0 = auto */ \
-    X(rs_bwd1_rpt, 0)  /* resample2d d_input1 tile kernel: pixel rows per thread, 0 = auto (4), 2 */ \
     X(rs_bwd1_fixed, 0)  /* resample2d d_input1 tile kernel: 0 = 32-bit fixed-point box cells (round 5), 2 = double cells */ \
     X(be_bwd_fixed, 0)  /* block_extractor / block attention shared-cell backward: 0 = 32-bit fixed-point accumulator cells (round 5), 2 = double cells */ \
     X(rs_bwd1_owned, 0)  /* resample2d d_input1, large calls: 0 = owned tiles + far complement, plain stores (round 6), 2 = the shared-cell tile kernel with its fold atomics (rounds 3-5) */ \
-    X(rs_bwd1_owned_min_pixels, 0)  /* owned tiles for calls of at least this many pixels (B H W); 0 = 2^18 */ \
-    X(rs_bwd1_owned_blocks, 0)  /* owned tiles: the channel slab is halved until the launch has this many blocks (0 = 1024) */ \
     X(warp_feat_fixed, 0)  /* warp d(feat) owned-tile kernel: 0 = double cells, 1 = 32-bit fixed-point cells (round 6 experiment: slower -- register spills) */ \
     X(conv_thin_variant, 0)  /* ffwm_conv_thin_forward (3 x 3): 0 = by shape, 1 / 2 = 8 / 16 output channels per lane, +4 = one input channel per step (no grouped prefetch) */ \
     X(ba_fwd_pix, 1)  /* block attention forward: 1-4 = ba_fwd_pix_kernel (channel-innermost boxes, coefficients in registers; pixel rows / channels per group / blocks per CU 8/4/4, 16/4/4, 8/8/4, 8/4/6: 65-86 us at cfg-5), 0 = rounds 3-5's be_fwd_lds_kernel<.., MODE 1> (98-117 us) */ \
     X(ba_bwd_fused, 3)  /* block attention backward, ba_bwd_src_kernel's tile rows / threads: 1 = 32 / 256, 2 = 16 / 256, 3 = 32 / 512 (tools/r06/ba_bwd_time.py) */ \
     X(ba_bwd_pix, 4)  /* ba_bwd_pix_kernel's pixel rows / channels per group / waves per SIMD: 0 = 16 / 4 / 3, 1 = 8 / 8 / 4, 2 = 16 / 4 / 4, 3 = 16 / 8 / 3, 4 = 8 / 4 / 4, 5 = 8 / 4 / 6 (tools/r06/ba_bwd_time.py); a value past the list is 0 */ \
-    X(be_bwd_flush, 0)  /* block_extractor / block attention shared-cell backward: 0 = every in-image cell by a global atomic, 1 = interior box cells by read-modify-write (round 6 experiment, slower) */ \
-    X(zero_fill_memset, 0)  /* 1 = zero_fill() calls hipMemsetAsync as rounds 1-4 did (diagnosis: reproduces the corrupted memset nodes) */ \
     X(conv_wgrad_unsliced, 0)  /* conv_bwd.hip tiled weight gradient: 1 = never cut the pixel range into slices (no zero-fill, no atomics: a diagnosis switch) */ \
     /* end of the list */
 

@@ -437,7 +437,7 @@ struct Wg2Plan {
     int64_t slices;
 };
 static Wg2Plan wg2_plan(int K, int N, int chunks_total) {
-    const int64_t wg_target = options().conv_wgrad_slice_target > 0 ? options().conv_wgrad_slice_target : 512;
+    const int64_t wg_target = 512;          // workgroups a launch is cut into along the pixels
     // pixel slices of a launch of `tiles` workgroup tiles: up to the target, at least 4 chunks each
     auto slices_for = [&](int64_t tiles) -> int64_t {
         int64_t sl = tiles >= wg_target ? 1 : wg_target / tiles;

@@ -46,7 +46,6 @@ struct ConvGeo {
     int Kd;                  // reduction length: C * R * S (MODE 1: C * 4)
     int N;                   // B * Ho * Wo
     int n_tiles, k_tiles;
-    int kfast;               // linear workgroup index: channel tiles fastest (1) or pixel tiles fastest (0)
     int splitk, chunks;      // chunks (of CPC input channels) per split
     long long out_bs;        // output batch stride in elements (split launch: K * oH * oW, the workspace slot's)
     long long out2_bs;       // second destination's batch stride (unsplit launches with out2 != NULL)
@@ -85,16 +84,10 @@ conv_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w, const 
     // Round 5: the (pixel tile, channel tile) pair comes from ONE linear index with the channel tiles fastest, XCD-remapped: the k_tiles
     // workgroups that gather the SAME activations are dispatched together on one XCD and meet in its L2.  (With blockIdx.x = pixel tile,
     // blockIdx.y = channel tile they ran a whole sweep of the pixels apart and every sweep re-fetched the input: PMC traffic 3.4-3.9 x
-    // the algorithmic bytes)  g.kfast == 0: the old mapping.
-    int n_tile, k_tile;
-    if (g.kfast) {
-        const unsigned t = xcd_remap(blockIdx.x, gridDim.x, 1);
-        k_tile = static_cast<int>(t % static_cast<unsigned>(g.k_tiles));
-        n_tile = static_cast<int>(t / static_cast<unsigned>(g.k_tiles));
-    } else {
-        n_tile = blockIdx.x % g.n_tiles;
-        k_tile = blockIdx.x / g.n_tiles;
-    }
+    // the algorithmic bytes)
+    const unsigned t = xcd_remap(blockIdx.x, gridDim.x, 1);
+    const int k_tile = static_cast<int>(t % static_cast<unsigned>(g.k_tiles));
+    const int n_tile = static_cast<int>(t / static_cast<unsigned>(g.k_tiles));
     const int n0 = n_tile * TN, k0 = k_tile * TM;
     // The bias of this wave's TM / 2 output channels, one per lane, loaded HERE: the epilogue fetches a register's channel from lane
     // a * 32 + jr + 4 half by ds_bpermute.  (A `bias[k]` load per register in the epilogue made each of its 16-64 stores wait for that
@@ -461,7 +454,6 @@ extern "C" int ffwm_conv2d_forward(const void* input, const void* weight, const 
     g.out2_bs = out2_batch_stride;
     g.act = act; g.slope = static_cast<float>(negative_slope);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    g.kfast = options().conv_fwd_kfast;
     const dim3 grid(static_cast<unsigned>(g.n_tiles) * static_cast<unsigned>(g.k_tiles), 1u, static_cast<unsigned>(g.splitk * classes));
     const double flops = 2.0 * B * g.Ho * g.Wo * classes * static_cast<double>(g.K) * g.Kd;
     const double bytes = 4.0 * (static_cast<double>(B) * C * H * W + static_cast<double>(K) * g.Kd * classes + static_cast<double>(B) * K * g.oH * g.oW);

@@ -141,7 +141,7 @@ rs_fwd_kernel(const T* __restrict__ in1, const T* __restrict__ in2, T* __restric
 // -fmad contraction of `val += yP * xP * in` (resample2d_kernel.cu:82-85) -- taps in the reference's order.
 constexpr int kRsBoxW = 80;
 
-template <int HALF, int RPT, bool DB>
+template <int HALF, int RPT>
 __global__ void __launch_bounds__(kBlock)
 rs_fwd_lds_kernel(const float* __restrict__ in1, const float* __restrict__ in2, float* __restrict__ out, int C,
                   int Hi, int Wi, int H, int W, int tiles_x, int tiles_y, int cslabs, int cs, int remap) {
@@ -154,7 +154,7 @@ rs_fwd_lds_kernel(const float* __restrict__ in1, const float* __restrict__ in2, 
     typedef float f32x4 __attribute__((ext_vector_type(4)));
     typedef float f32x2 __attribute__((ext_vector_type(2)));
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    f32x4* tile = reinterpret_cast<f32x4*>(smem_raw);          // [DB ? 2 : 1][NCELL]
+    f32x4* tile = reinterpret_cast<f32x4*>(smem_raw);          // [2][NCELL]
     __shared__ int red[4][NW];
     __shared__ int flag;
 
@@ -340,15 +340,9 @@ rs_fwd_lds_kernel(const float* __restrict__ in1, const float* __restrict__ in2, 
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, q3), ro3, obase[r], 0, 0);
             }
             if (more) {
-                if constexpr (DB) {
-                    commit(tile + (p ^ 1) * NCELL);
-                    __syncthreads();
-                    p ^= 1;
-                } else {                 // one buffer: other blocks of the CU cover the two barriers
-                    __syncthreads();
-                    commit(tile);
-                    __syncthreads();
-                }
+                commit(tile + (p ^ 1) * NCELL);
+                __syncthreads();
+                p ^= 1;
             }
         }
         return;
@@ -2022,35 +2016,28 @@ inline RsTiles plan_tiles(int64_t B, int64_t C, int64_t H, int64_t W, int tile_w
     return t;
 }
 
-// rs_fwd_variant -> the LDS-tile forward rs_fwd_lds_kernel<HALF, RPT, DB>: tiles of 64 x 4 RPT pixels (RPT 0 = by shape), two staging
-// buffers or one.  (1 = the direct-gather kernel: no entry of its own; a value beyond the table is "auto".)
-constexpr struct { int rpt; bool db; } kRsFwdLds[8] = {{0, true}, {0, true}, {4, true}, {1, true}, {2, true}, {2, false}, {4, false}, {1, false}};
-
 template <typename T>
 int launch_fwd(const T* in1, const T* in2, T* out, int64_t B, int64_t C, int64_t Hi, int64_t Wi,
                int64_t H, int64_t W, int ks, int dil, hipStream_t st) {
     const double bytes = sizeof(T) * static_cast<double>(B) * H * W * (2.0 * C + 3.0);
     const int remap = options().xcd_remap;
     const int half = ks / 2;
-    const int v = options().rs_fwd_variant;
     bool ok = true;          // false: a dispatch below found no kernel for its value
     if constexpr (sizeof(T) == 4) {
-        if (dil == 1 && half >= 1 && half <= 3 && v != 1) {
-            const auto cfg = kRsFwdLds[v >= 0 && v < 8 ? v : 0];
-            // measured: 64 x 8 tiles >= 64 x 16 > 64 x 4 at HBM-resident sizes
-            const int rpt = cfg.rpt ? cfg.rpt : (B * ((W + kTileX - 1) / kTileX) * ((H + 7) / 8) >= 2048 ? 2 : 1);
+        if (dil == 1 && half >= 1 && half <= 3) {
+            // rs_fwd_lds_kernel<HALF, RPT>: tiles of 64 x 4 RPT pixels, two staging buffers.  Measured: 64 x 8 tiles >= 64 x 16 > 64 x 4 at
+            // HBM-resident sizes
+            const int rpt = B * ((W + kTileX - 1) / kTileX) * ((H + 7) / 8) >= 2048 ? 2 : 1;
             LaunchScope ls("resample2d_fwd_lds", st, bytes);
             ok &= dispatch<1, 2, 3>(half, [&](auto HALF) {
-                return dispatch<4, 2, 1>(rpt, [&](auto RPT) {
-                    dispatch<true, false>(cfg.db, [&](auto DB) {
-                        constexpr int TH = 4 * RPT.value;
-                        const RsTiles t = plan_tiles(B, C, H, W, kTileX, TH);
-                        const size_t lds = static_cast<size_t>(DB.value ? 2 : 1) * (TH + 12) * kRsBoxW * 16;
-                        auto kfn = rs_fwd_lds_kernel<HALF.value, RPT.value, DB.value>;
-                        allow_large_lds(reinterpret_cast<const void*>(kfn));
-                        hipLaunchKernelGGL(kfn, dim3(t.grid), dim3(kBlock), lds, st, in1, in2, out, (int)C, (int)Hi, (int)Wi, (int)H, (int)W,
-                                           t.tiles_x, t.tiles_y, t.cslabs, t.cs, remap);
-                    });
+                return dispatch<2, 1>(rpt, [&](auto RPT) {
+                    constexpr int TH = 4 * RPT.value;
+                    const RsTiles t = plan_tiles(B, C, H, W, kTileX, TH);
+                    const size_t lds = static_cast<size_t>(2) * (TH + 12) * kRsBoxW * 16;
+                    auto kfn = rs_fwd_lds_kernel<HALF.value, RPT.value>;
+                    allow_large_lds(reinterpret_cast<const void*>(kfn));
+                    hipLaunchKernelGGL(kfn, dim3(t.grid), dim3(kBlock), lds, st, in1, in2, out, (int)C, (int)Hi, (int)Wi, (int)H, (int)W,
+                                       t.tiles_x, t.tiles_y, t.cslabs, t.cs, remap);
                 });
             });
             return ok ? check_launch("ffwm_resample2d_forward(lds)") : no_kernel("ffwm_resample2d_forward(lds)");
@@ -2077,7 +2064,6 @@ struct BwdRoute {
     // Round 6: owned tiles (rs_bwd1_owned_kernel + rs_bwd1_far_kernel, plain stores) for the calls the shared-cell tile kernel served:
     // fp32, dilation 1, kernel_size 2 / 4, >= 2^18 pixels, planes of >= 32 rows.  rs_bwd1_owned: 0 = on, 2 = off (rounds 3-5's kernels).
     bool owned;
-    int owned_min_blocks;
     bool clear1;           // every other path ACCUMULATES into grad_input1: an uninitialised buffer is cleared first
     // ks = 4, large calls, rs_bwd1_fixed = 2: the tile kernel when the flow is smooth, the tap-lane kernel when it is not --
     // rs_flow_irregular_kernel counts into `sel`, both are launched, one returns
@@ -2101,6 +2087,12 @@ struct BwdRoute {
     bool in2_lds;          // fp32, dilation 1, kernel_size 2 / 4 / 6
     bool in2_pixels;
 };
+// Owned tiles serve calls of at least kRsOwnedMinPixels pixels (B H W).  A block pays ~15 us for its pixels' weights (double-precision
+// exponentials) and the population count before its first channel, so the channel slab is halved only until the launch has
+// kRsOwnedMinBlocks blocks: slabs as large as two rounds of the 512 resident blocks allow ([8,64,512,512], 800 tiles: 32 channels
+// 722 us, 16: 815, 8: 907).
+constexpr int64_t kRsOwnedMinPixels = 1 << 18;
+constexpr int kRsOwnedMinBlocks = 1024;
 inline BwdRoute route_bwd(bool want1, bool want2, bool uninitialised, size_t esz, int64_t B, int64_t Hi, int64_t Wi, int64_t H, int64_t W,
                           int half, int dil, hipStream_t st) {
     const Options& o = options();
@@ -2111,15 +2103,12 @@ inline BwdRoute route_bwd(bool want1, bool want2, bool uninitialised, size_t esz
     const bool large = B * H * W >= (1 << 18) && H >= 32;
     BwdRoute r;
     r.owned = want1 && lds_tiles && half <= 2 && variant == 0 && o.rs_bwd1_owned != 2 &&
-              B * H * W >= (o.rs_bwd1_owned_min_pixels > 0 ? o.rs_bwd1_owned_min_pixels : (1 << 18)) && H >= 32 && Hi >= 32 &&
+              B * H * W >= kRsOwnedMinPixels && H >= 32 && Hi >= 32 &&
               Hi * Wi < (1LL << 29) && H * W < (1LL << 29);
-    // a block pays ~15 us for its pixels' weights (double-precision exponentials) and the population count before its first channel:
-    // slabs as large as two rounds of the 512 resident blocks allow ([8,64,512,512], 800 tiles: 32 channels 722 us, 16: 815, 8: 907)
-    r.owned_min_blocks = o.rs_bwd1_owned_blocks > 0 ? o.rs_bwd1_owned_blocks : 1024;
     const bool rest1 = want1 && !r.owned;
     r.clear1 = uninitialised && rest1;
     r.tile_fixed = o.rs_bwd1_fixed != 2;
-    r.tile_rpt = H >= 32 ? (o.rs_bwd1_rpt == 2 ? 2 : 4) : 1;
+    r.tile_rpt = H >= 32 ? 4 : 1;
     const bool tiles1 = rest1 && lds_tiles;
     const bool tile_only = tiles1 && (variant == 6 || (variant == 0 && r.tile_fixed)) && large;
     r.sel = tiles1 && half == 2 && variant == 0 && !tile_only && large ? static_cast<int*>(stream_scratch(st)) : nullptr;
@@ -2152,7 +2141,7 @@ int launch_bwd(const T* in1, const T* in2, const T* gout, T* gin1, T* gin2, int6
             LaunchScope ls("resample2d_bwd_input1_owned", st, bytes1);      // both launches: the tiles and their far complement
             ok &= dispatch<1, 2>(half, [&](auto HALF) {
                 using G = RsOwn<HALF.value>;
-                const RsTiles t = plan_tiles(B, C, Hi, Wi, G::OW, G::OH, r.owned_min_blocks);
+                const RsTiles t = plan_tiles(B, C, Hi, Wi, G::OW, G::OH, kRsOwnedMinBlocks);
                 hipLaunchKernelGGL((rs_bwd1_owned_kernel<HALF.value>), dim3(t.grid), dim3(G::THREADS), 0, st, (const float*)in2, (const float*)gout,
                                    (float*)gin1, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, quirk, overwrite ? 1 : 0, t.tiles_x, t.tiles_y, t.cslabs,
                                    t.cs, remap);
@@ -2204,7 +2193,7 @@ int launch_bwd(const T* in1, const T* in2, const T* gout, T* gin1, T* gin2, int6
             std::unique_ptr<LaunchScope> ls;
             if (!r.adaptive) ls.reset(new LaunchScope("resample2d_bwd_input1_tile", st, bytes1));
             ok &= dispatch<1, 2, 3>(half, [&](auto HALF) {
-                return dispatch<4, 2, 1>(r.tile_rpt, [&](auto RPT) {
+                return dispatch<4, 1>(r.tile_rpt, [&](auto RPT) {
                     dispatch<true, false>(r.tile_fixed, [&](auto FIXED) {
                         constexpr int TH = 4 * RPT.value;
                         const RsTiles t = plan_tiles(B, C, H, W, kTileX, TH);

@@ -108,7 +108,6 @@ __global__ void __launch_bounds__(256) zero_fill_kernel(unsigned* __restrict__ p
 int zero_fill(void* p, size_t bytes, hipStream_t st) {
     if (bytes == 0) return 0;
     if (!p || (bytes & 3u) || (reinterpret_cast<uintptr_t>(p) & 3u)) return 1;
-    if (options().zero_fill_memset) return hipMemsetAsync(p, 0, bytes, st) == hipSuccess ? 0 : 1;
     const size_t n = bytes / 4;
     size_t blocks = (n / 4 + 255) / 256;
     if (blocks < 1) blocks = 1;
@@ -124,7 +123,7 @@ Geometry plan(int64_t B, int64_t C, int64_t H, int64_t W, int cs_default) {
     g.tiles_x = static_cast<int>((W + kTileX - 1) / kTileX);
     g.tiles_y = static_cast<int>((H + kTileY - 1) / kTileY);
     const int64_t spatial = B * g.tiles_x * g.tiles_y;
-    int cs = options().channel_slab > 0 ? options().channel_slab : cs_default;
+    int cs = cs_default;
     if (cs > C) cs = static_cast<int>(C);
     g.cs = cs = halve_slab(cs, C, spatial, 4096, 1);   // >= 16 blocks per CU
     g.cslabs = static_cast<int>((C + cs - 1) / cs);

@@ -27,7 +27,7 @@ namespace {
 
 template <typename T, bool FLIP>
 __device__ __forceinline__ void warp_fwd_body(const T* __restrict__ feat, const T* __restrict__ flow, T* __restrict__ out, int C,
-                                              int Hi, int Wi, int H, int W, const TileCoord tc, int cs, int nt = 0) {
+                                              int Hi, int Wi, int H, int W, const TileCoord tc, int cs) {
     const int x = tc.xf, y = tc.yf;
     if (x >= W || y >= H) return;
     const size_t plane = static_cast<size_t>(H) * W;
@@ -66,13 +66,8 @@ __device__ __forceinline__ void warp_fwd_body(const T* __restrict__ feat, const 
             for (int q = 0; q < 4; ++q) v += s[u][q] * cn.w[q];
             ElemRow<T, 1> r;
             r.v[0] = v;
-            if (nt) {            // (wave-uniform) streaming stores: the output is read once, by a later kernel
-                buf_store_row_nt<T, 1>(make_rsrc(op + u * plane, obytes), o_direct, r);
-                if (FLIP) buf_store_row_nt<T, 1>(make_rsrc(op + u * plane + flip_planes, obytes), o_flip, r);
-            } else {
-                buf_store_row<T, 1>(make_rsrc(op + u * plane, obytes), o_direct, r);
-                if (FLIP) buf_store_row<T, 1>(make_rsrc(op + u * plane + flip_planes, obytes), o_flip, r);
-            }
+            buf_store_row<T, 1>(make_rsrc(op + u * plane, obytes), o_direct, r);
+            if (FLIP) buf_store_row<T, 1>(make_rsrc(op + u * plane + flip_planes, obytes), o_flip, r);
         }
     }
     for (; c < c1; ++c, fp += iplane, op += plane) {
@@ -113,7 +108,6 @@ struct WarpProblem {
 };
 struct WarpTable {
     int n;
-    int nt;              // streaming stores (options().warp_nt)
     WarpProblem p[kMaxWarpProblems];
 };
 
@@ -590,7 +584,6 @@ __device__ __forceinline__ void warp_bwd_body(const T* __restrict__ feat, const 
     const unsigned o_direct = static_cast<unsigned>(y * W + x) * static_cast<unsigned>(sizeof(T));
     const unsigned o_flip = static_cast<unsigned>(y * W + (W - 1 - x)) * static_cast<unsigned>(sizeof(T));
     const size_t flip_planes = static_cast<size_t>(C) * plane;
-    const bool options_pair_loads = pair_loads;
     T gix = 0, giy = 0;
 
     auto one = [&](const T g, const T s0, const T s1, const T s2, const T s3) {
@@ -606,7 +599,7 @@ __device__ __forceinline__ void warp_bwd_body(const T* __restrict__ feat, const 
     };
     int c = c0;
     if constexpr (sizeof(T) == 4) {
-        if (!gp && gflow && options_pair_loads) {
+        if (!gp && gflow && pair_loads) {
             // d(flow) alone, fp32: the two corners of a row are neighbours in memory, so ONE 8-byte load per row replaces two dword
             // gathers (4 instead of 6 vector memory instructions per pixel and channel) wherever, for every lane of the wave, a row
             // is either inside the image with both corners or outside with both (a lane at the left / right border has half a
@@ -701,12 +694,12 @@ warp_fwd_multi_kernel(const WarpTable tab) {
             const int ty = u % q.tiles_y;
             u /= q.tiles_y;
             warp_fwd_lds_body<FLIP>(static_cast<const float*>(q.feat), static_cast<const float*>(q.flow), static_cast<float*>(q.out), q.C,
-                                    q.Hi, q.Wi, q.H, q.W, tx, ty, static_cast<int>(u % q.cslabs), static_cast<int>(u / q.cslabs), q.cs, tab.nt, sh);
+                                    q.Hi, q.Wi, q.H, q.W, tx, ty, static_cast<int>(u % q.cslabs), static_cast<int>(u / q.cslabs), q.cs, /* nt = */ 0, sh);
             return;
         }
     }
     warp_fwd_body<T, FLIP>(static_cast<const T*>(q.feat), static_cast<const T*>(q.flow), static_cast<T*>(q.out), q.C, q.Hi, q.Wi,
-                           q.H, q.W, decode_tile_local(t, q.tiles_x, q.tiles_y, q.cslabs), q.cs, tab.nt);
+                           q.H, q.W, decode_tile_local(t, q.tiles_x, q.tiles_y, q.cslabs), q.cs);
 }
 
 // d(flow) of several warps in one launch (the pixel-major kernel with grad_feat == NULL).  The LDS-staged body is NOT used here:
@@ -724,7 +717,7 @@ warp_bwd_flow_multi_kernel(const WarpTable tab) {
     const unsigned t = xcd_remap(blockIdx.x - q.begin, (q.nblk + 7u) & ~7u, 1);
     if (t >= q.nblk) return;
     warp_bwd_body<T, FLIP>(static_cast<const T*>(q.feat), static_cast<const T*>(q.flow), static_cast<const T*>(q.gout), nullptr,
-                           static_cast<T*>(q.out), q.C, q.Hi, q.Wi, q.H, q.W, decode_tile_local(t, q.tiles_x, q.tiles_y, q.cslabs), q.cs, tab.nt != 0);
+                           static_cast<T*>(q.out), q.C, q.Hi, q.Wi, q.H, q.W, decode_tile_local(t, q.tiles_x, q.tiles_y, q.cslabs), q.cs, true);
 }
 
 // d(feat) without contended global atomics: a block owns `cg` whole (b, c) planes of grad_feat in LDS.
@@ -1470,7 +1463,7 @@ inline bool fwd_wants_lds(int64_t B, int64_t C, int64_t H, int64_t W, size_t esz
     return esz == 4 && (variant == 2 || (variant == 0 && H >= 64 && W >= 64 && B * C * H * W >= (1LL << 24)));
 }
 
-// Launch geometry of the LDS-tile kernels (kWlTileX x kWlTileY pixels): the channel slab starts at channel_slab or `cs_default` and is
+// Launch geometry of the LDS-tile kernels (kWlTileX x kWlTileY pixels): the channel slab starts at `cs_default` and is
 // halved down to `cs_floor` until the launch has `min_blocks` blocks.
 struct LdsTiles {
     int txs, tys, cs, cslabs;
@@ -1480,8 +1473,7 @@ inline LdsTiles plan_lds_tiles(int64_t B, int64_t C, int64_t H, int64_t W, int c
     LdsTiles t;
     t.txs = static_cast<int>((W + kWlTileX - 1) / kWlTileX);
     t.tys = static_cast<int>((H + kWlTileY - 1) / kWlTileY);
-    int cs = options().channel_slab > 0 ? options().channel_slab : cs_default;
-    if (cs > C) cs = static_cast<int>(C);
+    const int cs = cs_default < C ? cs_default : static_cast<int>(C);
     t.cs = halve_slab(cs, C, B * t.txs * t.tys, min_blocks, cs_floor);
     t.cslabs = static_cast<int>((C + t.cs - 1) / t.cs);
     t.grid = static_cast<unsigned>(B * t.txs * t.tys * t.cslabs);
@@ -1542,7 +1534,7 @@ struct BwdRoute {
     bool feat_tiles;       // fp32, planes beyond LDS, resolution kept: owned tiles + the far complement
     bool feat_pixels;      // the pixel-major kernel with global atomics (together with d(flow) when that is wanted too)
     // d(flow), at most one of:
-    bool flow_lds;         // d(flow) alone on LDS-staged tiles (warp_bwd_flow_lds_body) for the same tensors the forward takes there; warp_multi_lds = 1: never
+    bool flow_lds;         // d(flow) alone on LDS-staged tiles (warp_bwd_flow_lds_body) for the same tensors the forward takes there
     bool flow_pixels;      // the pixel-major kernel
     bool overwrite;        // the owned tiles STORE grad_feat (flipcat bit 1: it arrives uninitialised)
     bool clear_feat;       // ... every other path adds: the library clears it first
@@ -1556,7 +1548,7 @@ inline BwdRoute route_bwd(bool want_feat, bool want_flow, bool uninitialised, in
     r.feat_planes = want_feat && r.pp.ok && !atomics_only;
     r.feat_tiles = want_feat && !r.feat_planes && esz == 4 && Hi == H && Wi == W && !atomics_only;
     r.feat_pixels = want_feat && !r.feat_planes && !r.feat_tiles;
-    r.flow_lds = want_flow && !r.feat_pixels && options().warp_multi_lds != 1 && fwd_wants_lds(B, C, H, W, esz);
+    r.flow_lds = want_flow && !r.feat_pixels && fwd_wants_lds(B, C, H, W, esz);
     r.flow_pixels = want_flow && !r.flow_lds;
     r.overwrite = uninitialised && r.feat_tiles;
     r.clear_feat = uninitialised && want_feat && !r.feat_tiles;
@@ -1602,9 +1594,8 @@ int launch_bwd(const T* feat, const T* flow, const T* gout, T* gfeat, T* gflow, 
                 int gps = halve_slab(groups, groups, B * ntx * nty, 768, 1);
                 // ... and on towards ~12 blocks per CU while a block keeps >= 8 groups: two 8-wave blocks are resident per CU (119 registers),
                 // so 800 blocks of 32 groups ran as two rounds with the second 44 % empty -- [32,64,256,256]: 897 -> 782 us with 8 groups
-                // per block (tools/warp_feat_gps_sweep.py, profiles/r05_warp_feat_gps_sweep.txt; 4: 806, 2: 911)
+                // per block (profiles/r05_warp_feat_gps_sweep.txt; 4: 806, 2: 911)
                 gps = halve_slab(gps, groups, B * ntx * nty, 3072, 8);
-                if (options().warp_feat_gps > 0) gps = options().warp_feat_gps < groups ? options().warp_feat_gps : groups;
                 const int cslabs = (groups + gps - 1) / gps;
                 auto launch_far = [&]() {
                     LaunchScope ls(scope_at(flip ? "warp_flipcat_bwd_feat_far" : "warp_bwd_feat_far", Hi), st, esz * B * 2.0 * H * W);
@@ -1662,13 +1653,11 @@ int launch_bwd(const T* feat, const T* flow, const T* gout, T* gfeat, T* gflow, 
     return check_launch("ffwm_warp_backward");
 }
 
-// A problem of a multi FORWARD launch on LDS-staged tiles?  warp_multi_lds: 0 = auto (float, planes of >= 32 x 32 output pixels with
-// >= 32 channels: netG's three levels -- 31 vs 42 us warm, 49 vs 69 us cold for the launch, profiles/r04_warp_multi_lds_sweep.txt;
-// the 3-channel image warps stay on direct gathers), 1 = never, 2 = always (float).
+// A problem of a multi FORWARD launch on LDS-staged tiles?  Float, planes of >= 32 x 32 output pixels with >= 32 channels: netG's three
+// levels -- 31 vs 42 us warm, 49 vs 69 us cold for the launch, profiles/r04_warp_multi_lds_sweep.txt; the 3-channel image warps stay on
+// direct gathers.
 inline bool multi_wants_lds(const ffwm_warp_problem& pr, size_t esz) {
-    const int v = options().warp_multi_lds;
-    if (esz != 4 || v == 1) return false;
-    return v == 2 || (pr.H >= 32 && pr.W >= 32 && pr.C >= 32);
+    return esz == 4 && pr.H >= 32 && pr.W >= 32 && pr.C >= 32;
 }
 
 inline void fill_problem(WarpProblem& q, const ffwm_warp_problem& pr, int cs_default, unsigned begin, bool lds) {
@@ -1688,14 +1677,13 @@ inline void fill_problem(WarpProblem& q, const ffwm_warp_problem& pr, int cs_def
 }
 
 // Largest problem first: the workgroups of a launch are dispatched in index order, so the big level's tiles start at once and the
-// small levels fill the tail (longest-processing-time order; option warp_multi_order = 1 keeps the caller's order).
+// small levels fill the tail (longest-processing-time order).
 inline std::vector<int> multi_order(const ffwm_warp_problem* probs, int n) {
     std::vector<int> idx(n);
     for (int i = 0; i < n; ++i) idx[i] = i;
-    if (options().warp_multi_order == 0)
-        std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) {
-            return probs[a].B * probs[a].C * probs[a].H * probs[a].W > probs[b].B * probs[b].C * probs[b].H * probs[b].W;
-        });
+    std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) {
+        return probs[a].B * probs[a].C * probs[a].H * probs[a].W > probs[b].B * probs[b].C * probs[b].H * probs[b].W;
+    });
     return idx;
 }
 
@@ -1703,7 +1691,6 @@ template <typename T>
 int launch_fwd_multi(const ffwm_warp_problem* probs, int n, int flip, hipStream_t st) {
     WarpTable tab;
     tab.n = 0;
-    tab.nt = options().warp_nt;
     unsigned blocks = 0;
     double bytes = 0;
     auto flush = [&]() -> int {
@@ -1737,7 +1724,6 @@ int launch_fwd_multi(const ffwm_warp_problem* probs, int n, int flip, hipStream_
 
 template <typename T>
 int launch_bwd_multi(const ffwm_warp_problem* probs, int n, int flip, hipStream_t st) {
-    // (the d(flow) table below does not use the store policy)
     // d(feat): problems whose planes fit LDS and that share the channels-per-block of their plane plan go out together (one launch per
     // CG value: the step's seven image-warp problems are two launches); everything else one launch per problem (scope names carry the level)
     std::vector<bool> done(n, false);
@@ -1799,7 +1785,6 @@ int launch_bwd_multi(const ffwm_warp_problem* probs, int n, int flip, hipStream_
     // d(flow): every problem that wants it, one launch
     WarpTable tab;
     tab.n = 0;
-    tab.nt = options().warp_pair_loads;            // (the backward has no stores to stream: the field carries the pair-load switch)
     unsigned blocks = 0;
     double bytes = 0;
     auto flush = [&]() -> int {

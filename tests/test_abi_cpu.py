@@ -59,12 +59,15 @@ def test_argument_errors_are_reported_before_launch(hiplib):
     # options that no longer exist are unknown keys like any other
     assert hiplib.ffwm_set_option(b"ablate", 1) == -1 and b"unknown key" in hiplib.ffwm_last_error()
     assert hiplib.ffwm_set_option(b"conv_wgrad_prezeroed", 1) == -1
+    for key in REMOVED_OPTIONS:
+        assert hiplib.ffwm_set_option(key.encode(), 1) == -1 and b"unknown key" in hiplib.ffwm_last_error(), key
     # no option gives a negative value a meaning: refused, the option keeps its value (a negative return is always an error)
     assert hiplib.ffwm_set_option(b"xcd_remap", -1) == -1 and b"negative" in hiplib.ffwm_last_error()
     assert hiplib.ffwm_set_option(b"xcd_remap", 1) == 1
     from ffwm_amd import _lib
-    with pytest.raises(_lib.FFWMError):
-        _lib.set_option("ablate", 1)
+    for key in ("ablate",) + REMOVED_OPTIONS:
+        with pytest.raises(_lib.FFWMError):
+            _lib.set_option(key, 1)
     with pytest.raises(_lib.FFWMError):
         _lib.set_option("xcd_remap", -1)
     assert _lib.set_option("xcd_remap", 1) == 1
@@ -90,16 +93,18 @@ def test_argument_errors_are_reported_before_launch(hiplib):
 
 # every key of ffwm_set_option with its default (csrc/common.hpp generates struct Options and the key table from one list)
 OPTION_DEFAULTS = [
-    ("be_fwd_variant", 0), ("be_bwd_variant", 0), ("channel_slab", 0), ("xcd_remap", 1), ("scatter_variant", 0),
-    ("rows_per_thread", 0), ("warp_fwd_variant", 0), ("be_bwd_halo", 0), ("be_bwd_rows", 0), ("rs_fwd_variant", 0),
-    ("rs_bwd1_variant", 0), ("conv_tile_variant", 0), ("conv_wino_raw", 1), ("conv_fwd_split_target", 0),
-    ("conv_wgrad_slice_target", 0), ("conv_wino_ws", 0), ("conv_wino_split", 1), ("conv_thin_tail", 1), ("warp_nt", 0),
-    ("warp_pair_loads", 1), ("conv_wgrad_wino", 0), ("warp_multi_planes", 0), ("warp_multi_lds", 0), ("warp_multi_order", 0),
-    ("conv_fwd_kfast", 1), ("warp_feat_gps", 0), ("rs_bwd1_rpt", 0), ("rs_bwd1_fixed", 0), ("be_bwd_fixed", 0),
-    ("rs_bwd1_owned", 0), ("rs_bwd1_owned_min_pixels", 0), ("rs_bwd1_owned_blocks", 0), ("warp_feat_fixed", 0),
-    ("conv_thin_variant", 0), ("ba_fwd_pix", 1), ("ba_bwd_fused", 3), ("ba_bwd_pix", 4), ("be_bwd_flush", 0),
-    ("zero_fill_memset", 0), ("conv_wgrad_unsliced", 0),
+    ("be_fwd_variant", 0), ("be_bwd_variant", 0), ("xcd_remap", 1), ("scatter_variant", 0), ("warp_fwd_variant", 0),
+    ("be_bwd_halo", 0), ("be_bwd_rows", 0), ("rs_bwd1_variant", 0), ("conv_tile_variant", 0), ("conv_wino_raw", 1),
+    ("conv_fwd_split_target", 0), ("conv_wino_ws", 0), ("conv_wino_split", 1), ("conv_thin_tail", 1), ("conv_wgrad_wino", 0),
+    ("warp_multi_planes", 0), ("rs_bwd1_fixed", 0), ("be_bwd_fixed", 0), ("rs_bwd1_owned", 0), ("warp_feat_fixed", 0),
+    ("conv_thin_variant", 0), ("ba_fwd_pix", 1), ("ba_bwd_fused", 3), ("ba_bwd_pix", 4), ("conv_wgrad_unsliced", 0),
 ]
+# tuning switches that no test set, removed with the kernel arms only they reached: unknown keys now
+REMOVED_OPTIONS = (
+    "channel_slab", "rows_per_thread", "rs_fwd_variant", "conv_wgrad_slice_target", "warp_nt", "warp_pair_loads", "warp_multi_lds",
+    "warp_multi_order", "conv_fwd_kfast", "warp_feat_gps", "rs_bwd1_rpt", "rs_bwd1_owned_min_pixels", "rs_bwd1_owned_blocks",
+    "be_bwd_flush", "zero_fill_memset",
+)
 
 
 def test_option_table_keys_and_defaults(hiplib):
@@ -107,7 +112,8 @@ def test_option_table_keys_and_defaults(hiplib):
     loads the library and walks the literal list above (this process may have changed options in other tests)."""
     import subprocess
     import sys
-    assert len(OPTION_DEFAULTS) == len(set(k for k, _ in OPTION_DEFAULTS)) == 40
+    assert len(OPTION_DEFAULTS) == len(set(k for k, _ in OPTION_DEFAULTS)) == 25
+    assert len(REMOVED_OPTIONS) == 15 and not set(REMOVED_OPTIONS) & set(k for k, _ in OPTION_DEFAULTS)
     assert "FFWM_OPTS" not in os.environ, "FFWM_OPTS is set: the library would not start from its defaults"
     code = ("import sys; sys.path.insert(0, %r)\n"
             "from ffwm_amd import _lib\n"

@@ -179,7 +179,7 @@ def main():
               ("rs_bwd1.txt", "_resample2d_bwd_input1_variants.txt"), ("host_probe.txt", "_host_issue_vs_drain.txt"),
               ("two_stream_check.txt", "_multi_stream_check.txt"), ("bench_eager.json", "_bench_eager.json"),
               ("gf_trace.txt", "_guided_filter_kernels.txt"), ("ref_vs_hip.json", "_ref_vs_hip.json"),
-              ("warp_multi_lds_sweep.txt", "_warp_multi_lds_sweep_refresh.txt"), ("warp_bwd_flow_variants.txt", "_warp_bwd_flow_variants.txt"),
+              ("warp_bwd_flow_variants.txt", "_warp_bwd_flow_variants.txt"),
               ("dp_capture_probe.txt", "_dp_capture_probe.txt")]
     for a, b in copies:
         p = os.path.join(src, a)

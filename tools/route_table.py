@@ -66,20 +66,16 @@ def calls():
     for v in (1, 2, 9):
         add("be k3 160x160 fwd", {"be_fwd_variant": v}, be(1, 8, 160, 160, 3, src=False, flow=False))
         add("be k6 32x48 fwd", {"be_fwd_variant": v}, be(2, 8, 32, 48, 6, src=False, flow=False))
-    for v in (1, 2, 4):
-        add("be k3 160x160 fwd", {"rows_per_thread": v}, be(1, 8, 160, 160, 3, src=False, flow=False))
     add("be k3 1024x1024 fwd (nt stores)", {}, be(1, 8, 1024, 1024, 3, src=False, flow=False))
     for v in (1, 2, 3, 9):
         add("be k3 160x160 bwd", {"be_bwd_variant": v}, be(1, 8, 160, 160, 3, fwd=False))
         add("be k3 32x48 bwd", {"be_bwd_variant": v}, be(2, 8, 32, 48, 3, fwd=False))
     for opts in ({"be_bwd_halo": 8}, {"be_bwd_halo": 8, "be_bwd_variant": 2}, {"be_bwd_rows": 64, "be_bwd_variant": 2},
                  {"be_bwd_rows": 64, "be_bwd_variant": 2, "be_bwd_halo": 8}, {"be_bwd_rows": 64}, {"be_bwd_fixed": 2},
-                 {"be_bwd_fixed": 2, "be_bwd_halo": 8}, {"be_bwd_flush": 1}, {"channel_slab": 8}, {"channel_slab": 2},
-                 {"xcd_remap": 0}, {"scatter_variant": 1}):
+                 {"be_bwd_fixed": 2, "be_bwd_halo": 8}, {"xcd_remap": 0}, {"scatter_variant": 1}):
         add("be k3 160x160 bwd", opts, be(1, 8, 160, 160, 3, fwd=False))
     add("be k2 160x160 bwd", {"be_bwd_rows": 64, "be_bwd_variant": 2}, be(1, 8, 160, 160, 2, fwd=False))
     add("be k3 32x48", {"scatter_variant": 1}, be(2, 8, 32, 48, 3))
-    add("be k3 32x48", {"channel_slab": 2}, be(2, 8, 32, 48, 3))
     add("be k3 16x16 many channels (plane kernel, several channels per block)", {}, be(8, 512, 16, 16, 3, fwd=False))
 
     # ---------------------------------------------------------------- block attention
@@ -150,26 +146,18 @@ def calls():
     add("rs ks4 160x160 f64", {}, rs(1, 4, 160, 160, 4, dtype=torch.float64))
     add("rs ks4 160x160 dil2", {}, rs(1, 4, 160, 160, 4, dil=2))
     add("rs ks4 1024x1024 fwd", {}, rs(1, 4, 1024, 1024, 4, g1=False, g2=False))
-    for v in range(1, 8):
-        add("rs ks4 64x64 fwd", {"rs_fwd_variant": v}, rs(2, 8, 64, 64, 4, g1=False, g2=False))
-    add("rs ks2 64x64 fwd", {"rs_fwd_variant": 5}, rs(2, 8, 64, 64, 2, g1=False, g2=False))
-    add("rs ks6 64x64 fwd", {"rs_fwd_variant": 2}, rs(2, 8, 64, 64, 6, g1=False, g2=False))
     for name, shape in (("32x32", (2, 8, 32, 32)), ("512x512", (1, 8, 512, 512)), ("256x256", (2, 8, 256, 256))):
         for ks in (2, 4):
             add("rs ks%d %s g1 only" % (ks, name), {}, rs(*shape, ks, fwd=False, g2=False))
             add("rs ks%d %s g2 only" % (ks, name), {}, rs(*shape, ks, fwd=False, g1=False))
             add("rs ks%d %s overwrite" % (ks, name), {}, rs(*shape, ks, fwd=False, overwrite=True))
             for opts in ({"rs_bwd1_owned": 2}, {"rs_bwd1_owned": 2, "rs_bwd1_fixed": 2}, {"rs_bwd1_fixed": 2},
-                         {"rs_bwd1_owned": 2, "rs_bwd1_rpt": 2}, {"rs_bwd1_owned_min_pixels": 1 << 16},
-                         {"rs_bwd1_owned_min_pixels": 1 << 20}, {"rs_bwd1_owned_blocks": 256}, {"rs_bwd1_owned_blocks": 4096},
                          {"scatter_variant": 1}, {"scatter_variant": 2}, {"xcd_remap": 0}):
                 add("rs ks%d %s bwd" % (ks, name), opts, rs(*shape, ks, fwd=False))
             for v in (1, 2, 5, 6):
                 add("rs ks%d %s bwd" % (ks, name), {"rs_bwd1_variant": v}, rs(*shape, ks, fwd=False))
                 add("rs ks%d %s bwd" % (ks, name), {"rs_bwd1_variant": v, "rs_bwd1_fixed": 2}, rs(*shape, ks, fwd=False))
     add("rs ks4 512x512 bwd smooth", {"rs_bwd1_owned": 2, "rs_bwd1_fixed": 2}, rs(1, 8, 512, 512, 4, fwd=False, smooth=True))
-    add("rs ks6 512x512 bwd", {"rs_bwd1_fixed": 2, "rs_bwd1_rpt": 2}, rs(1, 8, 512, 512, 6, fwd=False))
-    add("rs ks4 64x64 fwd past the list", {"rs_fwd_variant": 8}, rs(2, 8, 64, 64, 4, g1=False, g2=False))
     add("rs ks6 32x32 many channels (plane kernel, several channels per block)", {}, rs(8, 512, 32, 32, 6, fwd=False, g2=False))
     add("rs ks4 32x32 strided", {}, rs(2, 8, 32, 32, 4, fwd=False, strided=True))
     add("rs ks4 32x32 strided f64 overwrite", {}, rs(2, 8, 32, 32, 4, dtype=torch.float64, fwd=False, strided=True, overwrite=True))
@@ -201,7 +189,6 @@ def calls():
         add("warp 200x200 -> 256x256" + tag, {}, wp(2, 8, 200, 200, 256, 256, flip))
         add("warp 4x16x512x512" + tag, {}, wp(4, 16, 512, 512, 512, 512, flip))
         add("warp 4x16x512x512 flow only" + tag, {}, wp(4, 16, 512, 512, 512, 512, flip, fwd=False, gfeat=False))
-        add("warp 4x16x512x512 flow only" + tag, {"warp_multi_lds": 1}, wp(4, 16, 512, 512, 512, 512, flip, fwd=False, gfeat=False))
         add("warp 256x256 feat only" + tag, {}, wp(2, 8, 256, 256, 256, 256, flip, fwd=False, gflow=False))
         add("warp 256x256 overwrite" + tag, {}, wp(2, 8, 256, 256, 256, 256, flip, fwd=False, overwrite=True))
         add("warp 32x32 overwrite" + tag, {}, wp(2, 8, 32, 32, 32, 32, flip, fwd=False, overwrite=True))
@@ -212,7 +199,7 @@ def calls():
         for v in (1, 3, 4):
             add("warp 256x256 bwd" + tag, {"warp_feat_fixed": v}, wp(2, 8, 256, 256, 256, 256, flip, fwd=False))
             add("warp 256x256 bwd overwrite" + tag, {"warp_feat_fixed": v}, wp(2, 8, 256, 256, 256, 256, flip, fwd=False, overwrite=True))
-        for opts in ({"warp_feat_gps": 1}, {"warp_feat_gps": 3}, {"scatter_variant": 1}, {"channel_slab": 8}, {"xcd_remap": 0}):
+        for opts in ({"scatter_variant": 1}, {"xcd_remap": 0}):
             add("warp 256x256" + tag, opts, wp(2, 8, 256, 256, 256, 256, flip))
         add("warp 2x64x256x256 bwd" + tag, {}, wp(2, 64, 256, 256, 256, 256, flip, fwd=False))
         add("warp 32x32" + tag, {"scatter_variant": 1}, wp(2, 8, 32, 32, 32, 32, flip))
@@ -247,8 +234,7 @@ def calls():
         add("warp multi 20 problems" + tag, {}, wm([(1, 3, 32)] * 20, flip))
         add("warp multi 2 / 4 / 8 channels per block" + tag, {}, wm([(512, 2, 16)] * 2 + [(512, 4, 16)] * 2 + [(128, 8, 16)] * 2, flip))
         add("warp multi with a large level" + tag, {}, wm([(2, 3, 64), (4, 16, 512)], flip))
-        for opts in ({"warp_multi_lds": 1}, {"warp_multi_lds": 2}, {"warp_multi_planes": 1}, {"warp_multi_order": 1}, {"warp_nt": 1},
-                     {"warp_nt": 2}, {"warp_pair_loads": 0}, {"scatter_variant": 1}, {"channel_slab": 8}):
+        for opts in ({"warp_multi_planes": 1}, {"scatter_variant": 1}):
             add("warp multi" + tag, opts, wm(net, flip))
     # ---------------------------------------------------------------- conv_winograd.hip
     def wino(B, C, H, W, K, dgrad=False, act=0, bias=False, reuse=False):
@@ -326,7 +312,6 @@ def calls():
     add("conv_fwd 3x3 s1 6x256x7x7 -> 512 (split, 49-pixel planes: scalar reduce)", {}, cf(6, 256, 7, 7, 512, 3, 1, 1, 0))
     add("conv_fwd 3x3 s1 2x32x8x8 -> 64 unaligned destination", {}, cf(2, 32, 8, 8, 64, 3, 1, 1, 0, odd_dst=True))
     add("conv_fwd 3x3 s1 2x32x8x8 -> 64", {"conv_fwd_split_target": 128}, cf(2, 32, 8, 8, 64, 3, 1, 1, 0))
-    add("conv_fwd 3x3 s1 2x32x8x8 -> 64", {"conv_fwd_kfast": 0}, cf(2, 32, 8, 8, 64, 3, 1, 1, 0))
 
     # ---------------------------------------------------------------- conv_bwd.hip, conv_wgrad.hip, conv_wgrad_wino.hip
     def wg(B, C, H, W, K, k, stride, pad, tiled=True, bias=False, prezeroed=False):
@@ -347,7 +332,6 @@ def calls():
         add("wgrad tiled %s 8x96x32x32 -> 128 (sliced)" % name, {}, wg(8, 96, 32, 32, 128, k, stride, pad))
         add("wgrad tiled %s 8x96x32x32 -> 128" % name, {"conv_wgrad_unsliced": 1}, wg(8, 96, 32, 32, 128, k, stride, pad))
         add("wgrad tiled %s 8x96x32x32 -> 128 prezeroed" % name, {}, wg(8, 96, 32, 32, 128, k, stride, pad, bias=True, prezeroed=True))
-        add("wgrad tiled %s 8x96x32x32 -> 128" % name, {"conv_wgrad_slice_target": 128}, wg(8, 96, 32, 32, 128, k, stride, pad))
         add("wgrad generic %s 2x24x9x9 -> 40" % name, {}, wg(2, 24, 9, 9, 40, k, stride, pad, tiled=False))
     add("wgrad tiled 3x3 s1 6x512x8x8 -> 512 (FlowNet's 8 x 8 layers)", {}, wg(6, 512, 8, 8, 512, 3, 1, 1))
 

@@ -1,6 +1,6 @@
 """resample2d d_input1 at BASELINE configs[0] ([1,64,128,128], ks 4, flow ~ U[-3,3)) and at [8,64,512,512]: the tap-lane kernel (option
-rs_bwd1_variant 0 = default, 5 = 16-row tiles) against round 2's plane / tile kernels (1 = plane where it fits, 2 = tile) and channel
-slabs; HIP-event time of the backward launches."""
+rs_bwd1_variant 0 = default, 5 = 16-row tiles) against round 2's plane / tile kernels (1 = plane where it fits, 2 = tile);
+HIP-event time of the backward launches."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -15,17 +15,14 @@ for shape in ((1, 64, 128, 128), (8, 64, 512, 512)):
     go = torch.rand(*shape, generator=g).to(dev)
     g1 = torch.zeros_like(in1)
     for variant in (0, 5, 1, 2):
-        for slab in ((0, 16) if variant in (0, 5) else (0,)):
-            lib.ffwm_set_option(b"rs_bwd1_variant", variant)
-            lib.ffwm_set_option(b"channel_slab", slab)
-            for _ in range(2):
-                ops.resample2d_backward(in1, in2, go, 4, 1, g1, None)
-            torch.cuda.synchronize()
-            _lib.prof_reset(); _lib.prof_enable(True)
-            for _ in range(5):
-                ops.resample2d_backward(in1, in2, go, 4, 1, g1, None)
-            torch.cuda.synchronize(); _lib.prof_enable(False)
-            rows = _lib.prof_collect()
-            print(shape, "variant", variant, "slab", slab, {k: round(v["avg_ms"] * 1e3, 1) for k, v in rows.items()})
+        lib.ffwm_set_option(b"rs_bwd1_variant", variant)
+        for _ in range(2):
+            ops.resample2d_backward(in1, in2, go, 4, 1, g1, None)
+        torch.cuda.synchronize()
+        _lib.prof_reset(); _lib.prof_enable(True)
+        for _ in range(5):
+            ops.resample2d_backward(in1, in2, go, 4, 1, g1, None)
+        torch.cuda.synchronize(); _lib.prof_enable(False)
+        rows = _lib.prof_collect()
+        print(shape, "variant", variant, {k: round(v["avg_ms"] * 1e3, 1) for k, v in rows.items()})
     lib.ffwm_set_option(b"rs_bwd1_variant", 0)
-    lib.ffwm_set_option(b"channel_slab", 0)

@@ -16,10 +16,9 @@ sm = torch.stack((3 * torch.sin(3.1 * yy + 0.3) * torch.cos(2.3 * xx), 3 * torch
                   torch.full((S, S), 2.0)), 0).unsqueeze(0).repeat(B, 1, 1, 1).contiguous().to(dev)
 go = torch.rand(B, C, S, S, generator=g).to(dev)
 res = {}
-for variant, fixed, rpt in ((0, 2, 0), (6, 2, 0), (6, 0, 0), (6, 0, 2), (6, 2, 2)):
+for variant, fixed in ((0, 2), (6, 2), (6, 0)):
     _lib.set_option("rs_bwd1_variant", variant)
     _lib.set_option("rs_bwd1_fixed", fixed)
-    _lib.set_option("rs_bwd1_rpt", rpt)
     for name, fl in (("random", rnd), ("smooth", sm)):
         g1 = torch.zeros_like(in1)
         for _ in range(2):
@@ -29,11 +28,10 @@ for variant, fixed, rpt in ((0, 2, 0), (6, 2, 0), (6, 0, 0), (6, 0, 2), (6, 2, 2
         for _ in range(3):
             ops.resample2d_backward(in1, fl, go, 4, 1, g1, None)
         torch.cuda.synchronize(); _lib.prof_enable(False)
-        print("variant %d cells %s rows/thread %d %s" % (variant, "fixed " if fixed == 0 else "double", rpt or 4, name), {k: round(v["avg_ms"] * 1e3, 1) for k, v in _lib.prof_collect().items()}, flush=True)
-        res[(variant, fixed, name)] = g1 / 3 if rpt == 0 else res.get((variant, fixed, name))
+        print("variant %d cells %s %s" % (variant, "fixed " if fixed == 0 else "double", name), {k: round(v["avg_ms"] * 1e3, 1) for k, v in _lib.prof_collect().items()}, flush=True)
+        res[(variant, fixed, name)] = g1 / 3
 _lib.set_option("rs_bwd1_variant", 0)
 _lib.set_option("rs_bwd1_fixed", 0)
-_lib.set_option("rs_bwd1_rpt", 0)
 for name in ("random", "smooth"):
     a, b = res[(6, 2, name)], res[(6, 0, name)]
     print(name, "fixed-point vs double cells (tile kernel): max abs diff / (1 + max|ref|) = %.3g" % float((a - b).abs().max() / (1 + a.abs().max())), flush=True)

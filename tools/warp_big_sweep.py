@@ -20,11 +20,11 @@ amp = 6.0 / S
 fl = torch.stack((xx + amp * torch.sin(3.1 * yy + 0.3) * torch.cos(2.3 * xx), yy + amp * torch.cos(2.7 * xx - 0.2) * torch.sin(1.9 * yy)), 0).unsqueeze(0).repeat(B, 1, 1, 1).contiguous().cuda()
 o = torch.empty(B, 2 * C, S, S, device="cuda")
 nbytes = 4.0 * B * S * S * (3 * C + 2)
-for opts in ({}, {"channel_slab": 8}, {"channel_slab": 32}, {"channel_slab": 64}, {"xcd_remap": 0}, {"channel_slab": 32, "xcd_remap": 0}):
+for opts in ({}, {"xcd_remap": 0}):
     for k, v in opts.items(): _lib.set_option(k, v)
     us = t(lambda: ops.warp_forward(feat, fl, True, out=o))
     print("%-40s %8.1f us  %5.2f TB/s  %.3f" % (opts, us, nbytes / us / 1e6, nbytes / us / 1e6 / 8))
-    _lib.set_option("channel_slab", 0); _lib.set_option("xcd_remap", 1)
+    _lib.set_option("xcd_remap", 1)
 go = torch.rand(B, 2 * C, S, S, device="cuda")
 gfe, gfl = torch.zeros_like(feat), torch.zeros_like(fl)
 us = t(lambda: ops.warp_backward(feat, fl, go, True, gfe, gfl), 5)

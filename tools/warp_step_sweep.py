@@ -1,5 +1,5 @@
 """netG's three warp + flip + cat levels at batch 8 as the train step issues them (multi-problem launches): forward, d(flow), d(feat)
-under the library's tuning options.  HIP-event time per launch."""
+with the XCD remap on / off and on the LDS-staged forward (warp_fwd_variant = 2).  HIP-event time per launch."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -38,20 +38,10 @@ def run(tag, cold):
 
 
 for cold in (False, True):
-    for slab in (0, 8, 32, 64):
-        for remap in (1, 0):
-            lib.ffwm_set_option(b"channel_slab", slab)
-            lib.ffwm_set_option(b"xcd_remap", remap)
-            run("slab %d remap %d" % (slab, remap), cold)
-lib.ffwm_set_option(b"channel_slab", 0); lib.ffwm_set_option(b"xcd_remap", 1)
+    for remap in (1, 0):
+        lib.ffwm_set_option(b"xcd_remap", remap)
+        run("remap %d" % remap, cold)
+lib.ffwm_set_option(b"xcd_remap", 1)
 lib.ffwm_set_option(b"warp_fwd_variant", 2)
 run("fwd LDS variant", False); run("fwd LDS variant", True)
 lib.ffwm_set_option(b"warp_fwd_variant", 0)
-for nt in (0, 1):
-    lib.ffwm_set_option(b"warp_nt", nt)
-    run("nt stores %d" % nt, False); run("nt stores %d" % nt, True)
-lib.ffwm_set_option(b"warp_nt", 0)
-for order in (1, 0, 1, 0):
-    lib.ffwm_set_option(b"warp_multi_order", order)
-    run("order %s" % ("caller's" if order else "largest first"), False); run("order %s" % ("caller's" if order else "largest first"), True)
-lib.ffwm_set_option(b"warp_multi_order", 0)
