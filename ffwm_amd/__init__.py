@@ -8,6 +8,9 @@ csyxwei/FFWM: hand-written HIP kernels behind the reference's own operator API.
     ffwm_amd.build               hipcc build recipe for ffwm_amd/lib/libffwm_hip.so
     ffwm_amd.Frontalizer         inference as the reference's test_ffwm.py runs it: flowNetF -> WarpNet -> netG from two
                                  checkpoints, one captured hipGraph (ffwm_amd.ffwm_eval; FoldedFFWM is the generator alone)
+    ffwm_amd.FaceIdentifier      the rest of that loop: Frontalizer -> (centre-face crop) -> LightCNN-29 feature -> cosine top-k
+                                 against a gallery, one captured hipGraph (ffwm_amd.identity_eval; FoldedLightCNN is the feature
+                                 network alone, IdentityResult what a call returns, RankMeter the by-pose rank-1 meter)
 """
 __version__ = "0.1.0"
 
@@ -17,4 +20,7 @@ def __getattr__(name):
     if name in ("Frontalizer", "FoldedFFWM", "FrontalizerResult"):
         from . import ffwm_eval
         return getattr(ffwm_eval, name)
+    if name in ("FaceIdentifier", "FoldedLightCNN", "IdentityResult", "RankMeter"):
+        from . import identity_eval
+        return getattr(identity_eval, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

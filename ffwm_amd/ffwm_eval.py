@@ -77,6 +77,19 @@ class _Spec(object):
         return n
 
 
+def conv_route(L, x, act):
+    """Which kernel serves the convolution L (a layer tuple with w, k, stride, pad) on input x (a tensor or a _Spec): the predicates
+    of conv.py, no thresholds here.  Shared by FoldedFFWM and identity_eval.FoldedLightCNN."""
+    from . import conv
+    K, C = L.w.shape[0], L.w.shape[1]
+    if L.k == 3 and L.stride == 1 and L.pad == 1 and min(C, K) >= 32 and conv.winograd_ok(x, L.w, act):
+        return "winograd"                                   # conv.winograd_eligible + winograd_ok
+    if (L.k in (3, 4) and L.stride in (1, 2) and L.pad < L.k and min(C, K) >= 32 and (L.stride == 2 or L.k == 3)
+            and conv.fwd_route_ok(x, L.w) and (L.stride == 2 or x.shape[2] <= 32)):
+        return "conv_mfma"                                  # conv.fwd_eligible + MfmaFwdConv2d's condition
+    return "vendor_conv"
+
+
 # ------------------------------------------------------------------------------------------------ the three executors
 class _PlanExec(object):
     """Shapes only: records (layer name, kind) of every launch the HIP executor would issue."""
@@ -340,15 +353,7 @@ class FoldedFFWM(object):
     # ---- routes -------------------------------------------------------------------------------------------------------
     def _route(self, name, x, act):
         """Which kernel serves convolution `name` on input x (a tensor or a _Spec): the predicates of conv.py, no thresholds here."""
-        from . import conv
-        L = self.layers[name]
-        K, C = L.w.shape[0], L.w.shape[1]
-        if L.k == 3 and L.stride == 1 and L.pad == 1 and min(C, K) >= 32 and conv.winograd_ok(x, L.w, act):
-            return "winograd"                                   # conv.winograd_eligible + winograd_ok
-        if (L.k in (3, 4) and L.stride in (1, 2) and L.pad < L.k and min(C, K) >= 32 and (L.stride == 2 or L.k == 3)
-                and conv.fwd_route_ok(x, L.w) and (L.stride == 2 or x.shape[2] <= 32)):
-            return "conv_mfma"                                  # conv.fwd_eligible + MfmaFwdConv2d's condition
-        return "vendor_conv"
+        return conv_route(self.layers[name], x, act)
 
     # ---- the forward, once for all executors ----------------------------------------------------------------------------
     def _res_block(self, ex, path, x, gate=None):

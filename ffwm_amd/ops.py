@@ -935,6 +935,72 @@ def bias_relu_forward(h, bias, out=None):
     return y
 
 
+# ---------------------------------------------------------------- identity evaluation (csrc/lightcnn_eval.hip)
+def mfm_tail(h, bias, residual=None, pool=False, out=None):
+    """pool(max(h[:, :C] + bias[:C], h[:, C:] + bias[C:]) + residual) of a contiguous float32 h [B, 2C, H, W] in one pass: the tail of a
+    LightCNN layer behind its convolution without bias.  bias [2C] or None, residual [B, C, H, W] or None, pool = MaxPool2d(2, 2,
+    ceil_mode=True).  out: a contiguous destination of the result's shape (a batch slice of a wider buffer, say)."""
+    _f32_in("mfm_tail", h, bias, residual, out)
+    if h.dim() != 4 or h.shape[1] % 2:
+        raise ValueError("mfm_tail: need [B, 2C, H, W], got %s" % (tuple(h.shape),))
+    B, C, H, W = h.shape[0], h.shape[1] // 2, h.shape[2], h.shape[3]
+    _bias_ok(h, bias, 2 * C)
+    if residual is not None and tuple(residual.shape) != (B, C, H, W):
+        raise ValueError("mfm_tail: the residual must be [%d, %d, %d, %d]" % (B, C, H, W))
+    shape = (B, C, (H + 1) // 2, (W + 1) // 2) if pool else (B, C, H, W)
+    if out is None:
+        out = h.new_empty(shape)
+    elif tuple(out.shape) != shape:
+        raise ValueError("mfm_tail: the destination must be %s" % (shape,))
+    if out.numel():
+        with _on_device(h) as stream:
+            _lib.check(_lib.load().ffwm_mfm_tail_forward(_ptr(h), _ptr(bias), _ptr(residual), _ptr(out), B, C, H, W, int(bool(pool)),
+                                                         _lib.F32, stream), "ffwm_mfm_tail_forward")
+    return out
+
+
+def identity_input(img, crop=False, out=None):
+    """The identity network's input [B, 1, H, W] from img [B, Cin, H, W] in one launch: the channel mean, or with crop=True (128 x 128
+    only) the reference's mean -> WarpNet(build_grid(B, 98)) -> F.interpolate(., (128, 128), mode="bilinear") (models/losses.py:85-112)."""
+    _f32_in("identity_input", img, out)
+    if img.dim() != 4 or img.shape[1] < 1:
+        raise ValueError("identity_input: need [B, Cin, H, W], got %s" % (tuple(img.shape),))
+    B, Cin, H, W = img.shape
+    if crop and (H, W) != (128, 128):
+        raise ValueError("identity_input: the centre-face crop is defined for 128 x 128 images only")
+    if out is None:
+        out = img.new_empty((B, 1, H, W))
+    elif tuple(out.shape) != (B, 1, H, W):
+        raise ValueError("identity_input: the destination must be [%d, 1, %d, %d]" % (B, H, W))
+    if out.numel():
+        with _on_device(img) as stream:
+            _lib.check(_lib.load().ffwm_identity_input(_ptr(img), _ptr(out), B, Cin, H, W, int(bool(crop)), _lib.F32, stream),
+                       "ffwm_identity_input")
+    return out
+
+
+def cosine_topk(probe, gallery, k):
+    """-> (values [B, k] float32 descending, indices [B, k] int32): the k largest torch.cosine_similarity(gallery, probe[b]) per probe row;
+    equal similarities: the lower gallery index first; NaN ranks above everything (topk's rule).  1 <= k <= min(G, 32), D <= 1024."""
+    _f32_in("cosine_topk", probe, gallery)
+    if probe.dim() != 2 or gallery.dim() != 2 or probe.shape[1] != gallery.shape[1]:
+        raise ValueError("cosine_topk: probe [B, D] and gallery [G, D] expected")
+    (B, D), G, k = probe.shape, gallery.shape[0], int(k)
+    if not (1 <= k <= min(G, 32)) or not (1 <= D <= 1024) or B < 1:
+        raise ValueError("cosine_topk: 1 <= k <= min(G, 32), 1 <= D <= 1024 and B >= 1 expected (B %d, G %d, D %d, k %d)" % (B, G, D, k))
+    lib = _lib.load()
+    need = lib.ffwm_cosine_topk_workspace_bytes(B, G, D, k)
+    if need <= 0:
+        raise ValueError("cosine_topk: the library refuses B %d, G %d, D %d, k %d" % (B, G, D, k))
+    ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=probe.device)
+    values = probe.new_empty((B, k))
+    indices = torch.empty((B, k), dtype=torch.int32, device=probe.device)
+    with _on_device(probe) as stream:
+        _lib.check(lib.ffwm_cosine_topk(_ptr(probe), _ptr(gallery), _ptr(values), _ptr(indices), B, G, D, k, _ptr(ws), ws.numel() * 4,
+                                        _lib.F32, stream), "ffwm_cosine_topk")
+    return values, indices
+
+
 # ---------------------------------------------------------------- fused L1 terms (csrc/l1_loss.hip)
 class _L1Problem(ctypes.Structure):            # include/ffwm_hip.h: ffwm_l1_problem
     _fields_ = [("x", ctypes.c_void_p), ("y", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("grad_x", ctypes.c_void_p),

@@ -597,6 +597,25 @@ int ffwm_upsample2x_bilinear_forward(const void* x, void* y, int64_t B, int64_t 
 int ffwm_sigmoid_gate_forward_strided(const void* a, const void* b, const void* x, void* att, void* y, int64_t B, int64_t C,
                                       int64_t HW, int64_t y_batch_stride, int dtype, void* stream);
 
+/* ---- identity evaluation (csrc/lightcnn_eval.hip): float32 only, FFWM_ERR_DTYPE otherwise ----------------------------------
+ * The tail of a LightCNN layer as one pass: h [B, 2C, H, W] is the convolution without its bias, bias [2C] or NULL, residual
+ * [B, C, H, W] or NULL, pool 0 / 1 = MaxPool2d(2, 2, ceil_mode=True) (a window that hangs over the edge takes its in-bounds elements):
+ *     y = pool(max(h[:, :C] + bias[:C], h[:, C:] + bias[C:]) + residual),   y [B, C, H, W] or [B, C, ceil(H / 2), ceil(W / 2)]
+ * contiguous.  Equal to the PyTorch composition bit for bit; NaN propagates as in ATen's maximum and max_pool2d. */
+int ffwm_mfm_tail_forward(const void* h, const void* bias, const void* residual, void* y, int64_t B, int64_t C, int64_t H, int64_t W,
+                          int pool, int dtype, void* stream);
+/* The identity network's input from img [B, Cin, H, W] into out [B, 1, H, W].  crop 0: the channel mean (a left-to-right sum, one
+ * division).  crop 1 (H = W = 128 only): mean -> WarpNet(build_grid(B, 98)) -> bilinear resize to 128 x 128 (models/losses.py:85-112)
+ * as one 16-tap gather per output pixel. */
+int ffwm_identity_input(const void* img, void* out, int64_t B, int64_t Cin, int64_t H, int64_t W, int crop, int dtype, void* stream);
+/* torch.cosine_similarity (eps 1e-8 on each norm) of probe [B, D] against gallery [G, D] and its k best per probe: values [B, k]
+ * float32 descending, indices [B, k] int32; equal similarities: the lower index first; a NaN similarity ranks above everything.
+ * 1 <= k <= min(G, 32), D <= 1024, B <= 65535.  Deterministic, no atomics.  workspace: 16-byte aligned, at least
+ * ffwm_cosine_topk_workspace_bytes (0 for sizes the entry refuses) bytes; nothing in it needs to be initialised. */
+int64_t ffwm_cosine_topk_workspace_bytes(int64_t B, int64_t G, int64_t D, int64_t k);
+int ffwm_cosine_topk(const void* probe, const void* gallery, void* values, void* indices, int64_t B, int64_t G, int64_t D, int64_t k,
+                     void* workspace, int64_t workspace_bytes, int dtype, void* stream);
+
 /* ---- built-in per-kernel timing (HIP events on the launch stream) ---------------------------
  * ffwm_prof_enable(1) brackets every kernel launch of this library with a pair of HIP events
  * recorded on the stream the kernel is launched on.  ffwm_prof_collect() waits for the recorded

@@ -1,0 +1,254 @@
+"""The identity evaluation of the reference's test_ffwm.py (frontalise -> LightCNN-29 feature -> rank against a gallery), two ways in
+ONE process, alternating:
+
+    python tools/identity_bench.py [--reps 5] [--seconds 0.5] [--out profiles/identity_eval.txt]
+
+(A) what the library offered before ffwm_amd/identity_eval.py: Frontalizer(graph=True), then nets.LightCNN29 eager on the channel mean
+    of fake_F128 (the path trainer.identity_feature takes), then torch.cosine_similarity + topk per probe row;
+(B) ffwm_amd.FaceIdentifier(graph=True): the frontaliser, the input kernel, FoldedLightCNN and the matcher in one captured hipGraph.
+
+Batch 1 and batch 8 against a 250-entry gallery.  Every shape is warmed first; a leg is timed with device events around as many calls as
+fill --seconds; the legs alternate A / B / A / B and each is reported as median and min-max over --reps repetitions.  Also: the crop
+(ATen grid_sample + interpolate on the channel mean against the one kernel), and -- the table FoldedLightCNN's routes rest on -- every
+convolution of the network that a hand-written kernel would serve, on that kernel and on the vendor's, at both batch sizes, as device
+time inside a captured graph (back-to-back eager calls of layers this small time the host's dispatch, not the kernels).  GPU only:
+without a device the tool fails.
+"""
+import argparse
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+import fill  # noqa: E402
+from frontalize_bench import kernel_events, time_leg  # noqa: E402
+
+DEV = "cuda:0"
+GALLERY = 250
+
+
+def graph_time(fn, calls=20, reps=7):
+    """Device ms per call of fn where FaceIdentifier runs it: `calls` back-to-back calls captured into one hipGraph (no host
+    dispatch between the kernels), the replay timed with device events; the median of `reps` replays."""
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s), torch.no_grad():
+        for _ in range(3):
+            fn()
+    torch.cuda.current_stream().wait_stream(s)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g), torch.no_grad():
+        for _ in range(calls):
+            fn()
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    times = []
+    for _ in range(reps + 2):
+        start.record()
+        g.replay()
+        stop.record()
+        stop.synchronize()
+        times.append(start.elapsed_time(stop) / calls)
+    return statistics.median(times[2:])
+
+
+def layer_table(folded, out):
+    """Per convolution and batch size: the route the predicates choose, its time and the vendor's on the same input."""
+    from ffwm_amd import identity_eval
+
+    class Recorder(identity_eval._HipExec):
+        def __init__(self, owner):
+            identity_eval._HipExec.__init__(self, owner)
+            self.inputs = {}
+
+        def layer(self, name, x, residual=None, pool=False):
+            self.inputs[name] = x
+            return identity_eval._HipExec.layer(self, name, x, residual, pool)
+
+    saved = identity_eval.VENDOR_LAYERS
+    identity_eval.VENDOR_LAYERS = frozenset()          # the table is about the predicates' own choice
+    rows = {}
+    try:
+        for B in (1, 8):
+            x = fill.image(B, 1, 128, 128, "lightcnn_in").to(DEV)
+            folded.arena.begin(x.device)
+            rec = Recorder(folded)
+            with torch.no_grad():
+                for _ in range(2):
+                    folded._run(rec, x)
+            torch.cuda.synchronize()
+            for name in folded.layer_names():
+                L, xin = folded.layers[name], rec.inputs[name]
+                route = folded._route(name, xin)
+                if route == "vendor_conv":
+                    continue
+
+                def own():
+                    folded.arena.begin(xin.device)
+                    return identity_eval.run_conv(folded, name, xin, route)
+
+                def vendor():
+                    return identity_eval.run_conv(folded, name, xin, "vendor_conv")
+                t_own, t_ven = graph_time(own), graph_time(vendor)
+                rows.setdefault(name, {})[B] = (route, tuple(xin.shape), t_own, t_ven)
+    finally:
+        identity_eval.VENDOR_LAYERS = saved
+    out("# convolutions a hand-written kernel would serve: device us per call on it / on the vendor's kernel (the layer alone, no tail), "
+        "each as 20 calls inside one captured graph, median of 7 replays -- no host dispatch between the kernels, as in FaceIdentifier")
+    keep_vendor = []
+    for name in folded.layer_names():
+        if name not in rows:
+            continue
+        cells, wins = [], []
+        for B in (1, 8):
+            if B in rows[name]:
+                route, shape, t_own, t_ven = rows[name][B]
+                cells.append("batch %d %s %s: %.1f / %.1f" % (B, "x".join(str(s) for s in shape[1:]), route, 1e3 * t_own, 1e3 * t_ven))
+                wins.append(t_ven < t_own)
+            else:
+                cells.append("batch %d: vendor by the predicates" % B)
+                wins.append(True)
+        if all(wins):
+            keep_vendor.append(name)
+        out("%-16s %s%s" % (name, "   ".join(cells), "   -> vendor wins at both" if all(wins) else ""))
+    out("# layers where the vendor's kernel wins at both batch sizes: %s" % (", ".join(keep_vendor) or "none"))
+    out("# identity_eval.VENDOR_LAYERS in this run: %s" % (", ".join(sorted(saved)) or "empty"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--seconds", type=float, default=0.5, help="length of one timed window")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "identity_eval.txt"))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("identity_bench: needs an MI355X; a CPU run measures nothing")
+
+    from ffwm_amd import FaceIdentifier, Frontalizer, nets, ops
+    from ffwm_amd.identity_eval import crop_grid
+
+    lines = []
+
+    def out(s=""):
+        print(s, flush=True)
+        lines.append(s)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+    flowNetF = fill.fill_module(nets.FlowNet(64)).to(DEV).eval()
+    netG = fill.fill_module(nets.FFWM(sn=True)).to(DEV).eval()
+    fill.boost_output_gain(netG)
+    torch.manual_seed(29)
+    light = nets.LightCNN29().to(DEV).eval()          # default initialisation: timing does not depend on the weights
+    front_a = Frontalizer(flowNetF, netG, graph=True)
+    ident = FaceIdentifier(flowNetF, netG, light, crop=False, graph=True, topk=1)
+    gallery_images = torch.cat([fill.image(50, 1, 128, 128, "gallery_%d" % i) for i in range(GALLERY // 50)], 0).to(DEV)
+    ident.set_gallery(["%04d" % i for i in range(GALLERY)], gallery_images)
+    gallery = ident.gallery_features
+
+    @torch.no_grad()
+    def leg_a(img):
+        r = front_a(img)
+        _, fea, _ = light(torch.mean(r.fake_F128, dim=(1,), keepdim=True))
+        sims, idxs = [], []
+        for b in range(fea.shape[0]):          # AverageMeter.update: one cosine_similarity + topk per probe
+            v, i = torch.cosine_similarity(gallery, fea[b:b + 1], dim=1).topk(k=10, dim=0)
+            sims.append(v)
+            idxs.append(i)
+        return fea, torch.stack(sims), torch.stack(idxs)
+
+    def leg_b(img):
+        r = ident(img)
+        return r.feature, r.top_sim, r.top_idx
+
+    out("# identity evaluation: frontalise -> LightCNN-29 feature -> top-10 of a %d-entry gallery, 128 x 128, float32, device %s"
+        % (GALLERY, torch.cuda.get_device_name(0)))
+    out("# A = Frontalizer(graph=True) + nets.LightCNN29 eager on the channel mean + torch.cosine_similarity / topk per probe row")
+    out("# B = FaceIdentifier(graph=True): frontaliser + input kernel + FoldedLightCNN + cosine_topk in one captured hipGraph")
+    out("# per leg: ms per call from device events over a window of >= %.2f s; %d repetitions, alternating A / B" % (args.seconds, args.reps))
+    layer_table(ident.net, out)
+    imgs = {B: fill.image(B, 3, 128, 128, "eval_img_S").to(DEV) for B in (1, 8)}
+    for B, img in imgs.items():          # warm every shape of both legs (solver selection, kept Winograd transforms, the captures)
+        for _ in range(3):
+            a, b = leg_a(img), leg_b(img)
+        torch.cuda.synchronize()
+        out("batch %d: max |A - B| feature %.3e (max |feature| %.3e), top similarities %.3e, top-1 indices equal: %s"
+            % (B, (a[0] - b[0]).abs().max().item(), a[0].abs().max().item(), (a[1] - b[1]).abs().max().item(),
+               bool(torch.equal(a[2][:, 0].cpu().long(), b[2][:, 0].cpu().long()))))
+    verdicts = {}
+    for B, img in imgs.items():
+        ms = {"A": [], "B": []}
+        calls = {}
+        leg_a(img), leg_b(img)                # the captures of this shape (a shape change re-captures)
+        torch.cuda.synchronize()
+        for _ in range(args.reps):
+            for name, fn in (("A", leg_a), ("B", leg_b)):
+                t, n = time_leg(lambda: fn(img), args.seconds)
+                ms[name].append(t)
+                calls[name] = n
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        spread = {k: max(v) - min(v) for k, v in ms.items()}
+        for k in ("A", "B"):
+            out("batch %d  %s  median %.3f ms  min %.3f  max %.3f  (%d calls per window)  runs [%s]"
+                % (B, k, med[k], min(ms[k]), max(ms[k]), calls[k], ", ".join("%.3f" % x for x in ms[k])))
+        margin, worst = med["A"] - med["B"], max(spread.values())
+        verdicts[B] = margin > worst
+        out("batch %d  A - B = %.3f ms against the larger min-max spread %.3f ms (A's own: %.3f): %s; A / B = %.2f"
+            % (B, margin, worst, spread["A"], "B is faster beyond the spread" if margin > worst else
+               ("B is not slower beyond the spread" if margin >= -worst else "B is SLOWER beyond the spread"), med["A"] / med["B"]))
+    out("# acceptance: B's median below A's by more than the spread at both batch sizes: %s"
+        % ("met" if all(verdicts.values()) else "MISSED (batch %s)" % ", ".join(str(b) for b, ok in verdicts.items() if not ok)))
+
+    # the crop alone: ATen's three steps against the one kernel
+    for B, img in imgs.items():
+        fake = ident(img).frontal.fake_F128.clone()
+        grid = crop_grid(B, device=DEV).permute(0, 2, 3, 1).contiguous()
+
+        @torch.no_grad()
+        def crop_a():
+            g = F.grid_sample(torch.mean(fake, dim=(1,), keepdim=True), grid, mode="bilinear", padding_mode="zeros", align_corners=False)
+            return F.interpolate(g, (128, 128), mode="bilinear")
+
+        def crop_b():
+            return ops.identity_input(fake, crop=True)
+        ca, cb = crop_a(), crop_b()
+        ms = {"A": [], "B": []}
+        for _ in range(args.reps):
+            for name, fn in (("A", crop_a), ("B", crop_b)):
+                ms[name].append(graph_time(fn))
+        out("batch %d  crop, device us per call inside a captured graph: ATen mean + grid_sample + interpolate median %.1f [%.1f .. %.1f], "
+            "identity_input(crop=True) %.1f [%.1f .. %.1f]; max abs diff %.2e"
+            % (B, 1e3 * statistics.median(ms["A"]), 1e3 * min(ms["A"]), 1e3 * max(ms["A"]), 1e3 * statistics.median(ms["B"]),
+               1e3 * min(ms["B"]), 1e3 * max(ms["B"]), (ca - cb).abs().max().item()))
+
+    for B in (1, 8):
+        plan = ident.plan(B)
+        kinds = {}
+        for _, k in plan:
+            kinds[k] = kinds.get(k, 0) + 1
+        out("batch %d  B LightCNN launches from plan(): %d  %s (inside one graph launch, with the frontaliser's, one input kernel and the "
+            "matcher's two)" % (B, len(plan), ", ".join("%s %d" % kv for kv in sorted(kinds.items()))))
+    for B, img in imgs.items():
+        n_a = kernel_events(lambda: leg_a(img))
+        n_b = kernel_events(lambda: leg_b(img))
+        out("batch %d  kernel events of one call (profiler): A %s (its frontaliser replays from a graph), B %s"
+            % (B, n_a if n_a is not None else "not measured", n_b if n_b is not None else "not measured"))
+    # where the LightCNN's own time goes at batch 1: the library's per-kernel timing of one eager forward
+    # where the LightCNN's own time goes at batch 1, inside a graph as FaceIdentifier runs it
+    x = fill.image(1, 1, 128, 128, "lightcnn_in").to(DEV)
+    with torch.no_grad():
+        p = ident.net._forward(x)[1].flatten(1).clone()
+    t_fc = graph_time(lambda: F.linear(p, ident.net.fc_w, None))
+    t_all = graph_time(lambda: ident.net._forward(x), calls=4)
+    out("batch 1  FoldedLightCNN inside a captured graph %.3f ms per forward; its F.linear (8192 -> 512, the vendor's GEMV) alone %.1f us "
+        "(20 calls in one graph): %s" % (t_all, 1e3 * t_fc, "it dominates: a hand-written GEMV is the next step" if t_fc > 0.25 * t_all else
+                                        "it does not dominate; the next step is the fused convolution + max-feature-map epilogue"))
+
+
+if __name__ == "__main__":
+    main()
