@@ -77,6 +77,10 @@ _SIGNATURES = {
     "ffwm_guided_filter_backward_general": [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, _i, _p],
     "ffwm_l1_multi": [_p, _i, _p, _p, _i, _i, _p],          # (array of ffwm_l1_problem, n, out, grad_out, n_slots, dtype, stream)
     "ffwm_conv3x3_winograd_weights_multi": [_p, _i, _i, _p],      # (array of ffwm_wino_weights, n, dtype, stream)
+    "ffwm_conv3x3_wg_weights": [_p, _p, _i64, _i64, _i, _i, _p],
+    "ffwm_conv3x3_wg_forward": [_p, _p, _p, _p, _p] + [_i64] * 5 + [_i, _p, _i, _p],
+    "ffwm_conv3x3_wg_forward_tiled": [_p, _p, _p, _p, _p] + [_i64] * 5 + [_i, _p, _i, _i, _p],
+    "ffwm_conv3x3_wg_tile": [_i64] * 5,
     "ffwm_mfm_tail_forward": [_p, _p, _p, _p] + [_i64] * 4 + [_i, _i, _p],
     "ffwm_identity_input": [_p, _p] + [_i64] * 4 + [_i, _i, _p],
     "ffwm_cosine_topk": [_p, _p, _p, _p] + [_i64] * 4 + [_p, _i64, _i, _p],
@@ -94,7 +98,8 @@ _SIGNATURES = {
 
 EXPORTS = sorted(list(_SIGNATURES) + ["ffwm_last_error", "ffwm_conv3x3_winograd_workspace_bytes", "ffwm_conv3x3_winograd_splits",
                                       "ffwm_conv2d_forward_workspace", "ffwm_guided_filter_workspace_bytes",
-                                      "ffwm_sampling_correctness_workspace_bytes", "ffwm_cosine_topk_workspace_bytes"])
+                                      "ffwm_sampling_correctness_workspace_bytes", "ffwm_cosine_topk_workspace_bytes",
+                                      "ffwm_conv3x3_wg_weights_bytes", "ffwm_conv3x3_wg_workspace_bytes"])
 
 
 class FFWMError(RuntimeError):
@@ -127,6 +132,10 @@ def load():
     lib.ffwm_sampling_correctness_workspace_bytes.restype = _i64
     lib.ffwm_cosine_topk_workspace_bytes.argtypes = [_i64] * 4
     lib.ffwm_cosine_topk_workspace_bytes.restype = _i64
+    lib.ffwm_conv3x3_wg_weights_bytes.argtypes = [_i64, _i64]
+    lib.ffwm_conv3x3_wg_weights_bytes.restype = _i64
+    lib.ffwm_conv3x3_wg_workspace_bytes.argtypes = [_i64] * 5
+    lib.ffwm_conv3x3_wg_workspace_bytes.restype = _i64
     lib.ffwm_last_error.argtypes = []
     lib.ffwm_last_error.restype = ctypes.c_char_p
     got = lib.ffwm_abi_version()

@@ -407,6 +407,161 @@ def route_conv_winograd(net):
     return n
 
 
+# ================================================================== frozen small-plane 3x3 layers (csrc/conv_winograd_gemm.hip)
+# The 3x3 / stride-1 layers of the two FROZEN loss networks on planes of 32 x 32 and below (VGG19 from relu3 on, LightCNN's later
+# stages) offer conv_winograd.hip a quarter of the chip's worth of work units; the vendor's VALU Winograd runs them at 35-60 TF.
+# Here they run as input transform -> 16 MFMA GEMMs -> output transform (bias + ReLU / bias + max-feature-map in the last launch,
+# the ReLU mask of the backward pass in the first), with U = G w G^T made ONCE per layer and direction.
+# FFWM_WINOGRAD_GEMM=0 turns the route off.
+_WG = _os.environ.get("FFWM_WINOGRAD_GEMM", "1") != "0"
+
+# (C, K) of the layer -> ((T_lo, T_hi) of the forward, (T_lo, T_hi) of the data gradient), T = B ceil(H / 2) ceil(W / 2) inclusive;
+# (1, 0) = never.  From tools/wino_gemm_layers.py (profiles/wino_gemm_layers.txt): every distinct frozen 3x3 shape of the train
+# step, 20 calls per captured graph, median of 7 replays; a shape is listed only where the three launches' median is below the
+# vendor convolution + its epilogue launch by more than the larger min-max spread of the two.  The ends of a range are measured
+# shapes; between two winners of one class the route is taken too.  What stays with the vendor: planes of 4 x 4 and below at batch 8
+# (T <= 40: three launches cost more than one), the 64- and 128-output-channel layers (the vendor is at 23-35 us there), and the
+# data gradients of 256 -> 512 and 512 -> 512 below 16 x 16 (margin inside the spread; 512 -> 512 at T = 128 wins by 2.4 us but its
+# neighbour at T = 160 does not, so the range starts at 512).  The 128 -> 256 data gradient is a CHOICE, not the measurement's
+# verdict: it wins at T = 2048 (59.6 -> 55.0 us, spread 3.8) and under LightCNN at T = 512 (28.9 -> 27.3), loses under VGG19's
+# ReLU mask at T = 512 and 640; the class is shared by both networks and is kept uniform, with the vendor.
+_WG_NEVER = (1, 0)
+WG_TABLE = {
+    (128, 256): ((512, 2048), _WG_NEVER),          # VGG conv3_1; LightCNN block4 / group4
+    (256, 256): ((512, 2048), (512, 2048)),        # VGG conv3_2-4
+    (256, 512): ((128, 512), (512, 512)),          # VGG conv4_1
+    (512, 512): ((128, 512), (512, 512)),          # VGG conv4_2-4, conv5_1
+    (96, 192): ((2048, 2048), _WG_NEVER),          # LightCNN block2
+    (96, 384): ((2048, 2048), (2048, 2048)),       # LightCNN group2
+    (192, 384): ((512, 512), (512, 512)),          # LightCNN block3
+    (192, 256): ((512, 512), (512, 512)),          # LightCNN group3
+}
+
+
+def _wg_class(weight):
+    return WG_TABLE.get((weight.shape[1], weight.shape[0]), (_WG_NEVER, _WG_NEVER))
+
+
+def _wg_in(t, rng):
+    return rng[0] <= t <= rng[1]
+
+
+def _wg_tiles(x):
+    return x.shape[0] * ((x.shape[2] + 1) // 2) * ((x.shape[3] + 1) // 2)
+
+
+def wg_entry(layer, weight, create=True):
+    """The transformed weights of a FROZEN layer, {0: U of the forward, 1: U of the data gradient -- only where WG_TABLE routes
+    the class's data gradient at all}, or None.  They live in the layer's __dict__ (they die with it), keyed by the weight's
+    version counter and address; they are built eagerly on the first call -- or by wg_prepare() when the trainer is built and
+    again when it captures -- and the building stream is synchronised, since the loss networks' passes run on side streams.  A
+    call made while a stream is capturing may READ a valid entry but never creates one: a transform that was only captured, not
+    run, must not be recorded as valid.  So weights loaded AFTER the entries were made (load_state_dict bumps the version
+    counter) are transformed again by the next eager call -- FFWMTrainer.capture() runs wg_prepare and its eager warm-up steps
+    first -- and a layer whose entry is stale inside a capture silently takes the vendor route for that graph, as frozen_cache's
+    layers re-transform per call.  Only a frozen nn.Parameter qualifies (see frozen_cache).  16 K (C rounded up to 16) floats
+    per direction: 0.25 GiB for the routed classes of VGG19 (170 MiB) and LightCNN-29 (87 MiB) together (wg_prepare returns
+    the bytes)."""
+    if (not isinstance(weight, nn.Parameter)) or weight.requires_grad or hasattr(layer, "weight_orig") or getattr(weight, "_ffwm_flat_adam", False):
+        return None
+    key = (weight._version, weight.data_ptr())
+    d = layer.__dict__.get("_wg_frozen")
+    if d is not None and d.get("key") == key:
+        return d
+    if not create or torch.cuda.is_current_stream_capturing():
+        return None
+    w = weight.detach().contiguous()
+    d = {"key": key, 0: ops.conv3x3_wg_weights(w, False)}
+    if _wg_class(weight)[1] != _WG_NEVER:
+        d[1] = ops.conv3x3_wg_weights(w, True)
+    torch.cuda.current_stream(weight.device).synchronize()
+    layer.__dict__["_wg_frozen"] = d
+    return d
+
+
+def wg_ok(x, weight, layer=None):
+    """Whether the frozen Conv2d(C, K, 3, 1, 1) `layer` runs x on the batched-GEMM Winograd route: fp32, no autocast, a frozen
+    nn.Parameter, and (T, C, K) inside WG_TABLE.  With `layer`, also that its transformed weights exist or may be made now."""
+    if not (_WG and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and weight.dtype == torch.float32
+            and isinstance(weight, nn.Parameter) and not weight.requires_grad and not torch.is_autocast_enabled()
+            and tuple(weight.shape[2:]) == (3, 3) and weight.shape[1] == x.shape[1]):
+        return False
+    if not _wg_in(_wg_tiles(x), _wg_class(weight)[0]):
+        return False
+    if layer is None:
+        return True
+    if not (layer.stride == (1, 1) and layer.padding == (1, 1) and layer.dilation == (1, 1) and layer.groups == 1
+            and layer.padding_mode == "zeros"):
+        return False
+    return wg_entry(layer, weight) is not None
+
+
+class _WgConv3x3(Function):
+    """A FROZEN Conv2d(C, K, 3, 1, 1) on csrc/conv_winograd_gemm.hip: relu(conv + bias) (relu=True; backward: the mask from the
+    saved output inside the input transform of the data gradient) or the bare convolution (LightCNN: bias + max-feature-map
+    follow as csrc/mfm.hip's kernels, whose backward needs both halves).  A data gradient outside WG_TABLE is the vendor's."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, entry, relu):
+        x = x.contiguous()
+        K, C = weight.shape[0], weight.shape[1]
+        y = ops.conv3x3_wg(x, entry[0], bias if relu else None, "relu" if relu else "none", K=K)
+        ctx.own_dgrad = 1 in entry and _wg_in(_wg_tiles(x), _wg_class(weight)[1])
+        ctx.save_for_backward(weight, y if relu else None, None if ctx.own_dgrad else x)
+        ctx.entry, ctx.relu, ctx.C = entry, relu, C
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        weight, y, x = ctx.saved_tensors
+        go = grad_y.contiguous()
+        if ctx.own_dgrad:
+            return ops.conv3x3_wg(go, ctx.entry[1], None, "none", relu_mask=y, K=ctx.C), None, None, None, None
+        if ctx.relu:
+            go = torch.ops.aten.threshold_backward(go, y, 0)
+        gx = torch.ops.aten.convolution_backward(go, x, weight, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1, [True, False, False])[0]
+        return gx, None, None, None, None
+
+
+def wg_bias_relu(x, layer):
+    """relu(layer(x)) of a frozen nn.Conv2d(C, K, 3, 1, 1) with a bias; the caller has checked wg_ok(x, layer.weight, layer)."""
+    entry = wg_entry(layer, layer.weight)
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _WgConv3x3.apply(x, layer.weight, layer.bias, entry, True)
+    return ops.conv3x3_wg(x.contiguous(), entry[0], layer.bias, "relu")
+
+
+def wg_conv(x, layer):
+    """The bare convolution (no bias) of a frozen layer, with autograd; the caller has checked wg_ok(x, layer.weight, layer)."""
+    entry = wg_entry(layer, layer.weight)
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _WgConv3x3.apply(x, layer.weight, None, entry, False)
+    return ops.conv3x3_wg(x.contiguous(), entry[0], None, "none", K=layer.weight.shape[0])
+
+
+def wg_bias_mfm(x, layer):
+    """max-feature-map(layer(x)) of a frozen layer where no gradient is asked for: one epilogue, the pre-activation is never stored."""
+    entry = wg_entry(layer, layer.weight)
+    return ops.conv3x3_wg(x.contiguous(), entry[0], layer.bias, "mfm", K=layer.weight.shape[0])
+
+
+def wg_prepare(net):
+    """Build the transformed weights of every layer of the frozen network `net` whose class WG_TABLE routes, now: the forward's,
+    and the data gradient's where the class's data gradient is routed (FFWMTrainer.__init__ and capture(): nothing is left to
+    create when the step is captured).  Layers with a valid entry cost nothing.  -> bytes held."""
+    n = 0
+    if not _WG:
+        return n
+    for m in net.modules():
+        if (isinstance(m, nn.Conv2d) and m.kernel_size == (3, 3) and m.stride == (1, 1) and m.padding == (1, 1) and m.dilation == (1, 1)
+                and m.groups == 1 and m.weight.is_cuda and m.weight.dtype == torch.float32 and _wg_class(m.weight)[0] != _WG_NEVER):
+            d = wg_entry(m, m.weight)
+            if d is not None:
+                n += 4 * sum(u.numel() for k, u in d.items() if k != "key")
+    return n
+
+
 # ================================================================================= MFMA forward (csrc/conv_fwd.hip)
 # The layers MIOpen serves through NHWC implicit-GEMM kernels wrapped in layout transposes and zero-fills -- stride-2
 # convolutions, 4x4 / stride-2 transposed convolutions, small-plane 3x3 layers with awkward channel counts (FlowNet's

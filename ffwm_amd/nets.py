@@ -350,6 +350,12 @@ class mfm(nn.Module):
                 if (f.kernel_size == (3, 3) and f.stride == (1, 1) and f.padding == (1, 1) and f.dilation == (1, 1) and f.groups == 1
                         and _WINOGRAD_MFM and _conv.winograd_ok(x, f.weight)):
                     h = _conv.winograd_conv(x, f)          # large planes: csrc/conv_winograd.hip
+                elif f.kernel_size == (3, 3) and _conv.wg_ok(x, f.weight, f):
+                    # frozen, small planes: Winograd as 16 MFMA GEMMs (csrc/conv_winograd_gemm.hip); without a gradient the bias and
+                    # the max-feature-map are its epilogue, with one the pre-activation is kept for csrc/mfm.hip's backward
+                    if f.bias is not None and not (torch.is_grad_enabled() and x.requires_grad):
+                        return _conv.wg_bias_mfm(x, f)
+                    h = _conv.wg_conv(x, f)
                 else:
                     h = F.conv2d(x, f.weight, None, f.stride, f.padding, f.dilation, f.groups)
             else:
@@ -459,6 +465,11 @@ class VGG19(nn.Module):
                         if not m.weight.requires_grad and _conv.winograd_ok(x, m.weight, 1):
                             # large planes: conv + bias + ReLU as ONE launch of the Winograd MFMA kernel (csrc/conv_winograd.hip)
                             x = _conv.winograd_bias_relu(x, m)
+                            i += 2
+                            continue
+                        if _conv.wg_ok(x, m.weight, m):
+                            # small planes: input transform, 16 MFMA GEMMs, output transform + bias + ReLU (csrc/conv_winograd_gemm.hip)
+                            x = _conv.wg_bias_relu(x, m)
                             i += 2
                             continue
                         h = F.conv2d(x, m.weight, None, m.stride, m.padding, m.dilation, m.groups)

@@ -749,6 +749,66 @@ def conv3x3_winograd_splits(B, C, H, W, K, act=0):
     return int(_lib.load().ffwm_conv3x3_winograd_splits(int(B), int(C), int(H), int(W), int(K), int(act)))
 
 
+# ---------------------------------------------------------------- Winograd as 16 batched GEMMs (csrc/conv_winograd_gemm.hip)
+WG_EPILOGUES = {"none": 0, "bias": 1, "relu": 2, "mfm": 3}
+
+
+def conv3x3_wg_weights(weight, data_gradient=False):
+    """U = G w G^T of a FROZEN Conv2d(C, K, 3, 1, 1) weight [K, C, 3, 3] for conv3x3_wg: the forward's, or (data_gradient) the
+    data gradient's (the weight transposed and rotated).  One launch; made once per layer and direction."""
+    if not (weight.is_cuda and weight.dtype == torch.float32 and weight.is_contiguous() and weight.dim() == 4 and tuple(weight.shape[2:]) == (3, 3)):
+        raise ValueError("conv3x3_wg_weights: a contiguous float32 [K, C, 3, 3] weight on the GPU")
+    K, C = (weight.shape[1], weight.shape[0]) if data_gradient else (weight.shape[0], weight.shape[1])
+    lib = _lib.load()
+    U = weight.new_empty((lib.ffwm_conv3x3_wg_weights_bytes(K, C) // 4,))
+    with _on_device(weight) as stream:
+        _lib.check(lib.ffwm_conv3x3_wg_weights(_ptr(weight), _ptr(U), K, C, int(bool(data_gradient)), _lib.F32, stream), "ffwm_conv3x3_wg_weights")
+    return U
+
+
+def conv3x3_wg(x, U, bias, epilogue, relu_mask=None, out=None, K=None, tile=0):
+    """Conv2d(C, K, 3, 1, 1) of x [B, C, H, W] with the transformed weights U of conv3x3_wg_weights, as input transform, 16 MFMA
+    GEMMs and output transform.  epilogue: "none", "bias", "relu" (bias + ReLU) or "mfm" (bias + max-feature-map: [B, K / 2, H, W]).
+    relu_mask: a tensor of x's shape; x is read as aten::threshold_backward(x, relu_mask, 0) (the data gradient behind a ReLU).
+    K: the output channels before the epilogue (default: bias.numel()).  tile (tests): 64 / 128 fixes the GEMM tile."""
+    _check("conv3x3_wg", x, relu_mask, out)
+    for t in (U, bias):
+        if t is not None and (t.device != x.device or t.dtype != x.dtype or not t.is_contiguous()):
+            raise ValueError("conv3x3_wg: U and bias must be contiguous tensors of the input's device and dtype")
+    if x.dtype != torch.float32:
+        raise TypeError("conv3x3_wg: float32 only")
+    B, C, H, W = x.shape
+    if K is None:
+        if bias is None:
+            raise ValueError("conv3x3_wg: K is needed when there is no bias")
+        K = bias.numel()
+    lib = _lib.load()
+    if U.numel() * 4 != lib.ffwm_conv3x3_wg_weights_bytes(K, C):
+        raise ValueError("conv3x3_wg: U does not belong to a layer with %d input and %d output channels" % (C, K))
+    if bias is not None and (not bias.is_contiguous() or bias.numel() != K):
+        raise ValueError("conv3x3_wg: bias must be a contiguous vector of %d elements" % K)
+    if relu_mask is not None and (relu_mask.shape != x.shape or not relu_mask.is_contiguous()):
+        raise ValueError("conv3x3_wg: relu_mask must be contiguous and of x's shape")
+    epi = WG_EPILOGUES[epilogue]
+    if epi == 3 and K % 2:
+        raise ValueError("conv3x3_wg: the mfm epilogue needs an even K")
+    shape = (B, K // 2 if epi == 3 else K, H, W)
+    if out is None:
+        out = x.new_empty(shape)
+    elif tuple(out.shape) != shape:
+        raise ValueError("conv3x3_wg: out has the wrong shape")
+    ws = x.new_empty((lib.ffwm_conv3x3_wg_workspace_bytes(B, C, H, W, K) // 4,))
+    with _on_device(x) as stream:
+        _lib.check(lib.ffwm_conv3x3_wg_forward_tiled(_ptr(x), _ptr(U), _ptr(bias), _ptr(out), _ptr(ws), B, C, H, W, K, epi,
+                                                     _ptr(relu_mask), int(tile), _dtype_code(x), stream), "ffwm_conv3x3_wg_forward")
+    return out
+
+
+def conv3x3_wg_tile(B, C, H, W, K):
+    """The GEMM tile (64 or 128) the plan of conv3x3_wg takes for this call on the current device: ffwm_conv3x3_wg_tile."""
+    return int(_lib.load().ffwm_conv3x3_wg_tile(int(B), int(C), int(H), int(W), int(K)))
+
+
 # ---------------------------------------------------------------- LightCNN max-feature-map
 def _mfm_dims(x):
     if x.dim() < 2 or x.shape[1] % 2:

@@ -234,6 +234,11 @@ class FFWMTrainer(object):
             fuse_spectral_norm(self.netD)
 
         broadcast_module_state([self.flowNetF, self.flowNetB, self.netG, self.netD, self.lightCNN, self.vgg])
+        self.wg_weight_bytes = 0
+        if self.device.type == "cuda":
+            # the frozen loss networks' small-plane 3x3 layers: transformed weights of the batched-GEMM Winograd route, once (conv.py)
+            from .conv import wg_prepare
+            self.wg_weight_bytes = wg_prepare(self.vgg) + wg_prepare(self.lightCNN)
 
         flow_params = [p for net in (self.flowNetF, self.flowNetB) for n, p in net.named_parameters()
                        if not n.startswith("inter_conv_occ")]
@@ -838,6 +843,8 @@ class FFWMTrainer(object):
         if mode == "segments" and os.environ.get("FFWM_SEG_STREAMS", "1") == "0":
             self._streams_saved = (self.flow_stream, self.loss_streams)          # (diagnosis: the five-graph step on one stream)
             self.flow_stream, self.loss_streams = None, None
+        from .conv import wg_prepare          # loss-network weights loaded since __init__: their transforms again, before any capture
+        self.wg_weight_bytes = wg_prepare(self.vgg) + wg_prepare(self.lightCNN)
         self._static = {k: v.clone() for k, v in b.items()}
         sb = self._static
         hooks_on = mode == "ingraph" and os.environ.get("FFWM_INGRAPH_HOOKS", "1") == "1"     # (0: all-reduces at the end of backward, still in-graph)

@@ -555,6 +555,33 @@ int ffwm_conv3x3_winograd_forward(const void* input, const void* weight, const v
                                   int64_t B, int64_t C, int64_t H, int64_t W, int64_t K, int data_gradient, int act,
                                   double slope, int dtype, void* stream);
 
+/* The same convolution in the classic three-launch form, for FROZEN layers on small planes (csrc/conv_winograd_gemm.hip): input
+ * transform, 16 independent fp32 MFMA GEMMs M_p = U_p V_p (one per Winograd position), output transform.  No atomics, no split of
+ * the reduction: deterministic.  float32 only.
+ *   ffwm_conv3x3_wg_weights: weight -> U = G w G^T, ffwm_conv3x3_wg_weights_bytes(K, C) bytes, stored [16][Cp / 4][K][4]
+ *     (Cp = C rounded up to 16, four input channels interleaved, channels past C zero).  K / C in the CALL's terms: data_gradient = 1 takes the layer's own
+ *     [C, K, 3, 3] transposed and rotated.  Made once per layer and direction; the forward call only reads it.
+ *   ffwm_conv3x3_wg_forward: input [B, C, H, W] -> output [B, K, H, W] (epilogue FFWM_WG_MFM: [B, K / 2, H, W], K even).
+ *     bias [K] or NULL (FFWM_WG_NONE ignores it).  relu_mask or NULL: a tensor of the input's shape; the input transform reads
+ *     input * (relu_mask > 0) as ATen's threshold_backward selects it (mask <= 0 -> 0, else the input: a NaN mask passes it) --
+ *     the data gradient behind a ReLU without the separate masking pass.  workspace: ffwm_conv3x3_wg_workspace_bytes(B, C, H, W, K)
+ *     bytes, 16-byte aligned, rewritten by every call (V and M).
+ *   ffwm_conv3x3_wg_tile: the GEMM tile (64 or 128) the plan of that call takes: 128 x 128 when that still gives every compute
+ *     unit a workgroup, else 64 x 64 (0 for a non-positive size).
+ *   ffwm_conv3x3_wg_forward_tiled: the same call with the GEMM tile fixed (tile = 64 or 128; 0 = the plan's): for tests and
+ *     measurements. */
+enum { FFWM_WG_NONE = 0, FFWM_WG_BIAS = 1, FFWM_WG_BIAS_RELU = 2, FFWM_WG_BIAS_MFM = 3 };
+int64_t ffwm_conv3x3_wg_weights_bytes(int64_t K, int64_t C);
+int64_t ffwm_conv3x3_wg_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W, int64_t K);
+int ffwm_conv3x3_wg_weights(const void* weight, void* U, int64_t K, int64_t C, int data_gradient, int dtype, void* stream);
+int ffwm_conv3x3_wg_forward(const void* input, const void* U, const void* bias, void* output, void* workspace,
+                            int64_t B, int64_t C, int64_t H, int64_t W, int64_t K, int epilogue, const void* relu_mask,
+                            int dtype, void* stream);
+int ffwm_conv3x3_wg_tile(int64_t B, int64_t C, int64_t H, int64_t W, int64_t K);
+int ffwm_conv3x3_wg_forward_tiled(const void* input, const void* U, const void* bias, void* output, void* workspace,
+                                  int64_t B, int64_t C, int64_t H, int64_t W, int64_t K, int epilogue, const void* relu_mask,
+                                  int tile, int dtype, void* stream);
+
 /* One Adam step (no weight decay, no amsgrad: torch.optim.Adam as models/ffwm_model.py:46-49 and
  * models/flownet_model.py:33 construct it) over FLAT float32 arrays of n elements, 16-byte aligned: parameters,
  * gradients, first and second moments.  `step` is the 1-based step count (bias corrections 1 - beta^step). */

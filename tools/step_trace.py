@@ -5,7 +5,8 @@ summed per category.  Prints wall per step (first kernel start -> last kernel en
     python tools/step_trace.py <kernel_trace.csv> [--steps 3] [--top 0]"""
 import argparse, collections, csv
 
-CATS = (("own winograd", ("winograd_conv", "winograd_weights", "conv3x3_thin")), ("vendor winograd", ("miopenSp3AsmConv",)),
+CATS = (("own winograd gemm (conv_wg_*)", ("wg_input_transform", "wg_batched_gemm", "wg_output_transform", "wg_weights_kernel")),
+        ("own winograd", ("winograd_conv", "winograd_weights", "conv3x3_thin")), ("vendor winograd", ("miopenSp3AsmConv",)),
         ("own wgrad 3x3", ("conv3x3_wgrad",)), ("own wgrad tiled", ("conv_wgrad_tile", "conv_wgrad_generic")),
         ("own conv_fwd (fwd + dgrad modes)", ("conv_fwd_kernel",)),
         ("igemm wrw", ("igemm_wrw",)), ("igemm bwd", ("igemm_bwd",)), ("igemm fwd", ("igemm_fwd",)), ("transposes", ("batched_transpose",)),

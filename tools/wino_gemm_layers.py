@@ -1,0 +1,151 @@
+"""Per-layer timing of the batched-GEMM Winograd route (csrc/conv_winograd_gemm.hip) against the vendor route it replaces, for
+every distinct frozen 3x3 / stride-1 layer shape of the train step's loss networks.
+
+Method (that of profiles/identity_eval.txt): 20 calls inside one captured graph, 7 replays, the median replay / 20 and the min-max
+spread of the seven.  Per shape and direction:
+  old   the vendor convolution + its epilogue launch (forward: bias + ReLU or bias + max-feature-map of csrc/mfm.hip;
+        data gradient: aten::threshold_backward + the vendor data gradient; LightCNN's data gradient has no mask on either side)
+  new   the three launches (the epilogue / the mask inside them)
+A shape is ROUTED only where new's median is below old's by more than the larger of the two spreads.  The last lines list, per
+(C, K) and direction, the T = B ceil(H / 2) ceil(W / 2) that won and lost: conv.WG_TABLE holds the ranges of the winners.
+
+    python tools/wino_gemm_layers.py [--out profiles/wino_gemm_layers.txt]
+"""
+import argparse
+import os
+import statistics
+import sys
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+CALLS, REPLAYS = 20, 7
+
+
+def step_shapes():
+    """(net, B, C, H, W, K) of every 3x3 / stride 1 / pad 1 layer the loss networks run in a train step at batch 8: VGG19 on the
+    128 px and 64 px images and on the 40 32 px crops, LightCNN-29 on the 128 px image -- listed by running them."""
+    from ffwm_amd import nets
+    seen, hooks = [], []
+    saved, nets.FUSED_ACTIVATIONS = nets.FUSED_ACTIVATIONS, False           # the modules' own forward: the hooks below see every conv
+    try:
+        vgg, light = nets.VGG19("relu5_1").cuda().eval(), nets.LightCNN29().cuda().eval()
+        for name, net in (("vgg", vgg), ("lightcnn", light)):
+            for m in net.modules():
+                if isinstance(m, nn.Conv2d) and m.kernel_size == (3, 3) and m.stride == (1, 1) and m.padding == (1, 1):
+                    def hook(mod, inp, out, name=name):
+                        x = inp[0]
+                        key = (name, x.shape[0], x.shape[1], x.shape[2], x.shape[3], mod.out_channels)
+                        if key not in seen:
+                            seen.append(key)
+                    hooks.append(m.register_forward_hook(hook))
+        with torch.no_grad():
+            for b, px in ((8, 128), (8, 64), (40, 32)):
+                vgg(torch.rand(b, 3, px, px, device="cuda"))
+            light(torch.rand(8, 1, 128, 128, device="cuda"))
+    finally:
+        nets.FUSED_ACTIVATIONS = saved
+        for h in hooks:
+            h.remove()
+    return seen
+
+
+def timed(fn):
+    """-> (median, min, max) microseconds per call."""
+    fn()
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(3):
+            fn()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(CALLS):
+            fn()
+    g.replay()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(REPLAYS):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        g.replay()
+        b.record()
+        torch.cuda.synchronize()
+        ts.append(a.elapsed_time(b) * 1000.0 / CALLS)
+    return statistics.median(ts), min(ts), max(ts)
+
+
+def measure(net, B, C, H, W, K):
+    from ffwm_amd import ops
+    relu = net == "vgg"
+    x = torch.randn(B, C, H, W, device="cuda")
+    w = torch.randn(K, C, 3, 3, device="cuda") / (9 * C) ** 0.5
+    b = torch.randn(K, device="cuda")
+    go = torch.randn(B, K, H, W, device="cuda")
+    y = torch.relu(torch.randn(B, K, H, W, device="cuda"))
+    Uf, Ub = ops.conv3x3_wg_weights(w, False), ops.conv3x3_wg_weights(w, True)
+    rows = {}
+    if relu:
+        rows["fwd"] = (timed(lambda: ops.bias_relu_forward(F.conv2d(x, w, None, 1, 1), b)),
+                       timed(lambda: ops.conv3x3_wg(x, Uf, b, "relu")))
+    else:
+        rows["fwd"] = (timed(lambda: ops.mfm_forward(F.conv2d(x, w, None, 1, 1), b)),
+                       timed(lambda: ops.conv3x3_wg(x, Uf, b, "mfm")))
+        rows["fwd+grad"] = (rows["fwd"][0], timed(lambda: ops.mfm_forward(ops.conv3x3_wg(x, Uf, None, "none", K=K), b)))
+
+    def vendor_dgrad(g):
+        return torch.ops.aten.convolution_backward(g, x, w, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1, [True, False, False])[0]
+    if relu:
+        rows["dgrad"] = (timed(lambda: vendor_dgrad(torch.ops.aten.threshold_backward(go, y, 0))),
+                         timed(lambda: ops.conv3x3_wg(go, Ub, None, "none", relu_mask=y, K=C)))
+    else:
+        rows["dgrad"] = (timed(lambda: vendor_dgrad(go)), timed(lambda: ops.conv3x3_wg(go, Ub, None, "none", K=C)))
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "wino_gemm_layers.txt"))
+    ap.add_argument("--max-tiles", type=int, default=2048, help="skip planes with more 2 x 2 tiles (the large-plane kernel's)")
+    ap.add_argument("--min-channels", type=int, default=64)
+    args = ap.parse_args()
+    from ffwm_amd import miopen_tuning
+    miopen_tuning.install()
+    lines = ["# tools/wino_gemm_layers.py: %d calls per captured graph, median of %d replays, microseconds per call; spread = max - min" % (CALLS, REPLAYS),
+             "# old = vendor convolution + epilogue launch, new = input transform + 16 MFMA GEMMs + output transform; TF = direct-equivalent of new",
+             "# ROUTED: new median < old median - max(spread old, spread new)",
+             "%-9s %3s %4s %3s %3s %4s %5s %-8s %9s %7s %9s %7s %6s  %s" % ("net", "B", "C", "H", "W", "K", "T", "dir", "old", "spread", "new", "spread", "TF", "")]
+    verdict = {}
+    for net, B, C, H, W, K in step_shapes():
+        T = B * ((H + 1) // 2) * ((W + 1) // 2)
+        if T > args.max_tiles or min(C, K) < args.min_channels:
+            continue
+        for d, (old, new) in measure(net, B, C, H, W, K).items():
+            win = new[0] < old[0] - max(old[2] - old[1], new[2] - new[1])
+            tf = 2.0 * 9 * B * H * W * C * K / new[0] * 1e-6
+            lines.append("%-9s %3d %4d %3d %3d %4d %5d %-8s %9.1f %7.1f %9.1f %7.1f %6.1f  %s" % (
+                net, B, C, H, W, K, T, d, old[0], old[2] - old[1], new[0], new[2] - new[1], tf, "ROUTED" if win else "vendor"))
+            print(lines[-1], flush=True)
+            if d != "fwd+grad":
+                verdict.setdefault((C, K), {}).setdefault(d, []).append((T, win))
+    lines.append("# per (C, K): T routed / T left with the vendor, forward | data gradient (conv.WG_TABLE)")
+    for ck, dirs in sorted(verdict.items()):
+        cells = []
+        for d in ("fwd", "dgrad"):
+            got = sorted(set(dirs.get(d, [])))
+            cells.append("%s / %s" % ([t for t, w in got if w], [t for t, w in got if not w]))
+        lines.append("#   %-10s: %s | %s" % (ck, cells[0], cells[1]))
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("\n".join(lines[-(len(verdict) + 1):]))
+
+
+if __name__ == "__main__":
+    main()
