@@ -2,7 +2,9 @@
 csyxwei/FFWM: hand-written HIP kernels behind the reference's own operator API.
 
     ffwm_amd.external_function   BlockExtractor / LocalAttnReshape / Resample2d (+Function.apply),
-                                 WarpNet, WarpFlipCat
+                                 WarpNet, WarpFlipCat, IdentityInputFunction (the identity network's input, --crop included)
+    ffwm_amd.losses              the reference's callers restated: AffineRegularizationLoss, PerceptualCorrectness,
+                                 IdentityLoss(lightcnn, crop) -- trainer.FFWMTrainer(..., crop=True) trains against the cropped face
     ffwm_amd.compat              block_extractor_cuda / local_attn_reshape_cuda / resample2d_cuda shims
     ffwm_amd.ops                 tensor-level calls into the C ABI (include/ffwm_hip.h)
     ffwm_amd.build               hipcc build recipe for ffwm_amd/lib/libffwm_hip.so

@@ -83,6 +83,7 @@ _SIGNATURES = {
     "ffwm_conv3x3_wg_tile": [_i64] * 5,
     "ffwm_mfm_tail_forward": [_p, _p, _p, _p] + [_i64] * 4 + [_i, _i, _p],
     "ffwm_identity_input": [_p, _p] + [_i64] * 4 + [_i, _i, _p],
+    "ffwm_identity_input_backward": [_p, _p] + [_i64] * 4 + [_i, _i, _p],
     "ffwm_cosine_topk": [_p, _p, _p, _p] + [_i64] * 4 + [_p, _i64, _i, _p],
     "ffwm_prof_enable": [_i],
     "ffwm_prof_collect": [],

@@ -11,6 +11,9 @@
 //                           maximum and max_pool2d propagate it (the pool's own rule: `val > max || isnan(val)`, in window order).
 //   ffwm_identity_input     the network's input: the channel mean, or (crop) mean -> WarpNet(build_grid(b, 98)) -> resize to 128 as
 //                           one 16-tap gather per output pixel.
+//   ffwm_identity_input_backward  its adjoint, for training against the cropped-face identity loss (models/losses.py:76-112 with
+//                           crop=True): grad_out / Cin into every channel, or (crop) A_y^T g A_x / Cin as two separable gather passes
+//                           through LDS -- no atomics, every element of grad_img written once, exact zeros outside the crop.
 //   ffwm_cosine_topk        cosine similarities of B probes against G gallery rows and the k best per probe, without float
 //                           atomics: a similarity pass (a wave per gallery row, eight probes per block held in LDS), a selection
 //                           per (probe, segment of the gallery), a merge per probe.  Selection is on 64-bit keys (ordered value,
@@ -216,8 +219,113 @@ __global__ void __launch_bounds__(kBlock) crop_kernel(const float* __restrict__ 
     out[(b * kFace + oy) * kFace + ox] = ly0 * row[0] + ly1 * row[1];
 }
 
+// ---- the input stage's gradient
+// crop 0: grad_img[b, c] = grad_out[b, 0] / Cin for every channel (the division the forward makes, one rounding).
+__global__ void __launch_bounds__(kBlock) gray_bwd_kernel(const float* __restrict__ go, float* __restrict__ gi, int64_t total, int Cin, int64_t HW) {
+    const float n = static_cast<float>(Cin);
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < total; i += static_cast<int64_t>(gridDim.x) * kBlock) {
+        const int64_t b = i / HW, o = i - b * HW;
+        const float v = go[i] / n;
+        float* p = gi + b * Cin * HW + o;
+        for (int c = 0; c < Cin; ++c) p[c * HW] = v;
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) gray4_bwd_kernel(const float4* __restrict__ go, float4* __restrict__ gi, int64_t total4, int Cin, int64_t HW4) {
+    const float n = static_cast<float>(Cin);
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < total4; i += static_cast<int64_t>(gridDim.x) * kBlock) {
+        const int64_t b = i / HW4, o = i - b * HW4;
+        const float4 g = go[i];
+        const float4 v = float4{g.x / n, g.y / n, g.z / n, g.w / n};
+        float4* p = gi + b * Cin * HW4 + o;
+        for (int c = 0; c < Cin; ++c) p[c * HW4] = v;
+    }
+}
+
+// The crop is separable: out = A_y gray A_x^T with, per axis, A = R S (S: the two-tap sample of plane index r at crop_coord(r), R: the
+// two-tap resize of output index o).  Its adjoint is a gather: input index i along an axis is touched by at most 5 output indices, all
+// within kCropCand consecutive ones from crop_first_candidate(i) on (the lowest touching index lies 1 .. 6 past it: one spare on either side).
+constexpr int kCropCand = 8;
+constexpr int kCropBand = 8;        // input rows per block of crop_bwd_kernel
+
+// twice_origin = 2 origin (55 rows, 29 columns): floor((i - origin) 128 97 / 98^2) - 3, the factor rounded to 331 / 256; all-integer
+__device__ __forceinline__ int crop_first_candidate(int i, int twice_origin) { return (((2 * i - twice_origin + 512) * 331) >> 9) - 331 - 3; }
+
+// A[o, i]: the weight of input index i in output index o along an axis, from the forward's own coordinates and weights (resize
+// coordinate clamped at 0, upper tap clamped at 97; crop_coord in double, rounded once).  0 when no tap of o is i -- the exact tap test.
+__device__ __forceinline__ float crop_axis_weight(int o, int i, double origin) {
+    if (o < 0 || o >= kFace) return 0.f;
+    const float scale = static_cast<float>(kCropPlane) / kFace;
+    float r = scale * (o + 0.5f) - 0.5f;
+    r = r < 0.f ? 0.f : r;
+    const int r0 = static_cast<int>(r);
+    const int r1 = r0 + (r0 < kCropPlane - 1 ? 1 : 0);
+    const float l1 = r - r0, l0 = 1.f - l1;
+    const int rs[2] = {r0, r1};
+    const float ls[2] = {l0, l1};
+    float w = 0.f;
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        const float y = crop_coord(rs[a], origin);
+        const float yf = floorf(y);
+        const int y0 = static_cast<int>(yf);
+        const float w1 = y - yf, w0 = (yf + 1.f) - y;
+        if (y0 == i) w += ls[a] * w0;
+        if (y0 + 1 == i) w += ls[a] * w1;
+    }
+    return w;
+}
+
+// grad_gray = A_y^T g A_x for a band of kCropBand input rows of one image, then / Cin into every channel.  Pass 1: t[Y][ox] = sum over
+// the candidate output rows oy (ascending) of A_y[oy, Y] g[oy][ox], kept in LDS; pass 2: sum over the candidate output columns ox
+// (ascending) of A_x[ox, X] t[Y][ox].  A fixed order and no atomics: bit-identical from run to run.  A cell no tap touches (rows
+// 0 .. 26 and 127, columns 0 .. 13 and 114 .. 127) adds nothing to 0.f and is stored as that.
+__global__ void __launch_bounds__(kBlock) crop_bwd_kernel(const float* __restrict__ go, float* __restrict__ gi, int Cin) {
+    __shared__ float wy[kCropBand][kCropCand];
+    __shared__ float wx[kCropCand][kFace];
+    __shared__ float t[kCropBand][kFace];
+    const int tid = threadIdx.x;
+    const int band = blockIdx.x * kCropBand;
+    const int64_t b = blockIdx.y;
+    const float* g = go + b * (kFace * kFace);
+    if (tid < kCropBand * kCropCand) {
+        const int yl = tid / kCropCand, k = tid % kCropCand;
+        wy[yl][k] = crop_axis_weight(crop_first_candidate(band + yl, 55) + k, band + yl, 27.5);
+    }
+    for (int i = tid; i < kCropCand * kFace; i += kBlock) {
+        const int k = i / kFace, X = i % kFace;
+        wx[k][X] = crop_axis_weight(crop_first_candidate(X, 29) + k, X, 14.5);
+    }
+    __syncthreads();
+    const int x = tid & (kFace - 1);
+    for (int yl = tid / kFace; yl < kCropBand; yl += kBlock / kFace) {
+        const int o0 = crop_first_candidate(band + yl, 55);
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < kCropCand; ++k) {
+            const float w = wy[yl][k];          // != 0 only for 0 <= o0 + k < 128
+            if (w != 0.f) s += w * g[(o0 + k) * kFace + x];
+        }
+        t[yl][x] = s;
+    }
+    __syncthreads();
+    const float n = static_cast<float>(Cin);
+    const int o0 = crop_first_candidate(x, 29);
+    for (int yl = tid / kFace; yl < kCropBand; yl += kBlock / kFace) {
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < kCropCand; ++k) {
+            const float w = wx[k][x];
+            if (w != 0.f) s += w * t[yl][o0 + k];
+        }
+        const float v = s / n;
+        float* p = gi + (b * Cin * kFace + band + yl) * kFace + x;
+        for (int c = 0; c < Cin; ++c) p[c * (kFace * kFace)] = v;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ cosine similarity + top-k
-constexpr int kProbes = 8;           // probes per block of the similarity pass
+constexpr int kProbes = 8;          // probes per block of the similarity pass
 constexpr int kSegment = 2048;       // gallery rows per selection block
 constexpr int kMaxSegments = 256;
 constexpr float kCosEps = 1e-8f;
@@ -413,6 +521,32 @@ extern "C" int ffwm_identity_input(const void* img, void* out, int64_t B, int64_
     } else {
         hipLaunchKernelGGL(gray_kernel, dim3(ew_grid(total)), dim3(kBlock), 0, st, static_cast<const float*>(img), static_cast<float*>(out),
                            total, static_cast<int>(Cin), HW);
+    }
+    return check_launch(fn);
+}
+
+extern "C" int ffwm_identity_input_backward(const void* grad_out, void* grad_img, int64_t B, int64_t Cin, int64_t H, int64_t W, int crop,
+                                            int dtype, void* stream) {
+    const char* fn = "ffwm_identity_input_backward";
+    FFWM_REQUIRE(dtype == FFWM_F32, FFWM_ERR_DTYPE, "%s: float32 only", fn);
+    FFWM_REQUIRE(grad_out && grad_img, FFWM_ERR_ARG, "%s: NULL tensor pointer", fn);
+    FFWM_REQUIRE(B > 0 && Cin >= 1 && H > 0 && W > 0, FFWM_ERR_ARG, "%s: sizes must be positive", fn);
+    FFWM_REQUIRE(crop == 0 || crop == 1, FFWM_ERR_ARG, "%s: crop must be 0 or 1", fn);
+    FFWM_REQUIRE(!crop || (H == kFace && W == kFace), FFWM_ERR_ARG, "%s: the centre-face crop is defined for 128 x 128 images only", fn);
+    FFWM_REQUIRE(Cin < (1 << 20) && H < (1 << 20) && W < (1 << 20) && B < (1LL << 40) / (Cin * H * W) && (!crop || B <= 65535), FFWM_ERR_SIZE,
+                 "%s: tensor too large", fn);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int64_t HW = H * W, total = B * HW;
+    LaunchScope ls(crop ? "identity_crop_bwd" : "identity_gray_bwd", st, 4.0 * (Cin + 1.0) * total);
+    if (crop) {
+        hipLaunchKernelGGL(crop_bwd_kernel, dim3(kFace / kCropBand, static_cast<unsigned>(B)), dim3(kBlock), 0, st,
+                           static_cast<const float*>(grad_out), static_cast<float*>(grad_img), static_cast<int>(Cin));
+    } else if (HW % 4 == 0 && (reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(grad_img)) % 16 == 0) {
+        hipLaunchKernelGGL(gray4_bwd_kernel, dim3(ew_grid(total / 4)), dim3(kBlock), 0, st, static_cast<const float4*>(grad_out),
+                           static_cast<float4*>(grad_img), total / 4, static_cast<int>(Cin), HW / 4);
+    } else {
+        hipLaunchKernelGGL(gray_bwd_kernel, dim3(ew_grid(total)), dim3(kBlock), 0, st, static_cast<const float*>(grad_out),
+                           static_cast<float*>(grad_img), total, static_cast<int>(Cin), HW);
     }
     return check_launch(fn);
 }

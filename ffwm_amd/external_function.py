@@ -316,6 +316,53 @@ class WarpFlipCat(nn.Module):
         return WarpFunction.apply(feat, flow, True)
 
 
+class IdentityInputFunction(Function):
+    """apply(img[B,Cin,H,W], crop) -> [B,1,H,W]: the identity network's input (ops.identity_input: the channel mean, or with crop
+    the reference's centre-face crop, models/losses.py:85-91) with its adjoint as the backward (ops.identity_input_backward).  The map
+    is linear and fixed: nothing but the shape is kept for the backward."""
+
+    @staticmethod
+    def forward(ctx, img, crop):
+        _require_cuda(img)
+        ctx.cin, ctx.crop = img.shape[1], bool(crop)
+        return ops.identity_input(img.contiguous(), ctx.crop)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        return ops.identity_input_backward(grad_output.contiguous(), ctx.cin, ctx.crop), None
+
+
+class IdentityInputManyFunction(Function):
+    """apply(crop, img_0, .., img_{n-1}) -> [n B,1,H,W], torch.cat of the n inputs' IdentityInputFunction results without the cat:
+    every launch writes its batch slice of the one result, and reads its slice of the gradient in the backward."""
+
+    @staticmethod
+    def forward(ctx, crop, *imgs):
+        _require_cuda(imgs[0])
+        B, _, H, W = imgs[0].shape
+        if any(tuple(u.shape[2:]) != (H, W) or u.shape[0] != B for u in imgs):
+            raise ValueError("identity_input_many: the images must agree in batch and plane size")
+        ctx.crop, ctx.cins, ctx.b = bool(crop), [u.shape[1] for u in imgs], B
+        out = imgs[0].new_empty((len(imgs) * B, 1, H, W))
+        for i, u in enumerate(imgs):
+            ops.identity_input(u.contiguous(), ctx.crop, out=out[i * B:(i + 1) * B])
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        g = grad_output.contiguous()
+        B = ctx.b
+        return (None,) + tuple(ops.identity_input_backward(g[i * B:(i + 1) * B], cin, ctx.crop) if ctx.needs_input_grad[1 + i] else None
+                               for i, cin in enumerate(ctx.cins))
+
+
+def identity_input_many(imgs, crop=False):
+    """cat([identity_input(u, crop) for u in imgs], 0), differentiable, one launch per image and direction."""
+    return IdentityInputManyFunction.apply(crop, *imgs)
+
+
 class GuidedFilterFunction(Function):
     """apply(x[B,1 or C,H,W], y[B,C,H,W], r, eps) -> GuidedFilter(r, eps)(x, y) of the reference
     (models/external_function.py:239-277), differentiable in x and y.  FFWM's own call (c_x == c_y, planes up to 128 x 128, y the

@@ -49,15 +49,15 @@ def crop_grid(b, d=98, dtype=torch.float32, device=None):
     return torch.stack((gx, gy), 0).unsqueeze(0).repeat(b, 1, 1, 1)
 
 
-def torch_identity_input(img, crop=False):
+def torch_identity_input(img, crop=False, grid=None):
     """ops.identity_input as the reference's PyTorch composition (any dtype and device): gray first, then the crop
-    (models/ffwm_model.py:196-200)."""
+    (models/ffwm_model.py:196-200).  grid: the sampling grid [B, 2, 98, 98] when it is not `crop_grid` in the image's own dtype."""
     gray = torch.mean(img, dim=(1,), keepdim=True)
     if not crop:
         return gray
     if tuple(img.shape[2:]) != (128, 128):
         raise ValueError("identity_input: the centre-face crop is defined for 128 x 128 images only")
-    warped = torch_warp(gray, crop_grid(img.shape[0], 98, img.dtype, img.device))
+    warped = torch_warp(gray, crop_grid(img.shape[0], 98, img.dtype, img.device) if grid is None else grid)
     return F.interpolate(warped, (128, 128), mode="bilinear")
 
 

@@ -7,6 +7,10 @@ kz = 3 / 5 / 7 on the 32 / 64 / 128 px flows.  Same constructor arguments, same 
 the two ops are the gfx950 kernels behind ``ffwm_amd.external_function``.  ``fused=True`` evaluates the
 same loss and its gradient with ONE kernel per scale (csrc/affine_reg.hip) instead of
 6 launches forward + ~10 backward per coordinate grid.
+
+``IdentityLoss`` (/root/reference/models/losses.py:76-112) is the identity term of FFWM's own training, with the ``--crop``
+option of train_ffwm.py: the network's input stage -- channel mean, centre-face crop, resize -- is one kernel per direction
+(csrc/lightcnn_eval.hip).
 """
 import torch
 import torch.nn as nn
@@ -262,6 +266,51 @@ def _exp_minus_one(dtype):
     if dtype not in _E1:
         _E1[dtype] = float(torch.exp(torch.tensor(-1.0, dtype=dtype)))
     return _E1[dtype]
+
+
+# ================================================================================= identity loss (csrc/lightcnn_eval.hip)
+def identity_network_input(img, crop=False):
+    """The identity network's input [B, 1, H, W] of img [B, Cin, H, W], differentiable: on float32 GPU tensors one kernel per
+    direction (external_function.IdentityInputFunction), everywhere else (CPU, float64, half) the PyTorch composition
+    `identity_eval.torch_identity_input`, which autograd differentiates."""
+    if img.is_cuda and img.dtype == torch.float32:
+        from .external_function import IdentityInputFunction
+        return IdentityInputFunction.apply(img, bool(crop))
+    from .identity_eval import crop_grid, torch_identity_input
+    if crop and img.dtype != torch.float32:
+        # the reference builds its grid in float32 and casts it (`build_grid(b, 98).type_as(out)`, models/losses.py:85): a float64 run
+        # samples at the float32 grid's coordinates, and so does this one
+        return torch_identity_input(img, True, grid=crop_grid(img.shape[0], 98, device=img.device).type_as(img))
+    return torch_identity_input(img, crop)
+
+
+class IdentityLoss(nn.Module):
+    """The reference's IdentityLoss (models/losses.py:76-112): same constructor, same forward(out, gt), same build_grid(b, d).
+        loss = L1(fc(out), fc(gt)) + L1(pool(out), pool(gt)),   (_, fc, pool) = lightcnn(input), the features of gt under no_grad
+    with the network's input the channel mean or, with crop=True (train_ffwm.py --crop), the centre-face crop resized back to the
+    image's size: WarpNet(build_grid(b, 98)) and a bilinear F.interpolate.  The reference warps and resizes the 3-channel image and
+    takes the mean last; here the mean comes first (as FFWMModel.test does, models/ffwm_model.py:196-200) and the crop runs on one
+    channel.  Both steps are linear and act on different axes -- the mean over channels, the crop over the plane -- so they commute and
+    the two orders differ by rounding only.  The crop is defined for 128 x 128 images."""
+
+    def __init__(self, lightcnn, crop=False):
+        super().__init__()
+        self.lightcnn = lightcnn
+        self.criterionL1 = torch.nn.L1Loss()
+        self.crop = crop
+
+    def forward(self, out, gt):
+        _, fc_out, pool_out = self.lightcnn(identity_network_input(out, self.crop))
+        with torch.no_grad():
+            _, fc_gt, pool_gt = self.lightcnn(identity_network_input(gt, self.crop))
+        loss = self.criterionL1(fc_out, fc_gt.detach())
+        loss = loss + self.criterionL1(pool_out, pool_gt.detach())
+        return loss
+
+    def build_grid(self, b, d):
+        """[b, 2, d, d]: linspace(-d // 2, d // 2, d) around the face centre (64, 77) of a 128 x 128 image, over 64."""
+        from .identity_eval import crop_grid
+        return crop_grid(b, d)
 
 
 # ================================================================================= fused L1 terms (csrc/l1_loss.hip)

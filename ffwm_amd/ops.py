@@ -1039,6 +1039,28 @@ def identity_input(img, crop=False, out=None):
     return out
 
 
+def identity_input_backward(grad_out, cin, crop=False, out=None):
+    """The adjoint of identity_input in one launch: grad_out [B, 1, H, W] -> d/d(img) [B, cin, H, W], overwritten (no zero-fill; `out`:
+    a contiguous destination of that shape).  crop=False: grad_out / cin in every channel; crop=True (128 x 128 only): the transposed
+    crop, a gather in a fixed order without atomics -- exactly 0 outside rows 27 .. 126 and columns 14 .. 113."""
+    _f32_in("identity_input_backward", grad_out, out)
+    cin = int(cin)
+    if grad_out.dim() != 4 or grad_out.shape[1] != 1 or cin < 1:
+        raise ValueError("identity_input_backward: need grad_out [B, 1, H, W] and cin >= 1, got %s, %d" % (tuple(grad_out.shape), cin))
+    B, _, H, W = grad_out.shape
+    if crop and (H, W) != (128, 128):
+        raise ValueError("identity_input_backward: the centre-face crop is defined for 128 x 128 images only")
+    if out is None:
+        out = grad_out.new_empty((B, cin, H, W))
+    elif tuple(out.shape) != (B, cin, H, W):
+        raise ValueError("identity_input_backward: the destination must be [%d, %d, %d, %d]" % (B, cin, H, W))
+    if out.numel():
+        with _on_device(grad_out) as stream:
+            _lib.check(_lib.load().ffwm_identity_input_backward(_ptr(grad_out), _ptr(out), B, cin, H, W, int(bool(crop)), _lib.F32, stream),
+                       "ffwm_identity_input_backward")
+    return out
+
+
 def cosine_topk(probe, gallery, k):
     """-> (values [B, k] float32 descending, indices [B, k] int32): the k largest torch.cosine_similarity(gallery, probe[b]) per probe row;
     equal similarities: the lower gallery index first; NaN ranks above everything (topk's rule).  1 <= k <= min(G, 32), D <= 1024."""

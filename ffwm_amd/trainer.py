@@ -150,9 +150,11 @@ class FFWMTrainer(object):
     def __init__(self, device, world_size=1, seed=0, titers=0, bucket_bytes=64 << 20, warp=None,
                  warp_flipcat=None, ngf=64, capturable=False, fused_spectral_norm=None, batched_losses=True,
                  mfma_wgrad=None, flat_adam=None, fused_bn=None, mfma_fwd=None, fused_l1=None, segmented_backward=False,
-                 force_collectives=False):
+                 force_collectives=False, crop=False):
         self.device = torch.device(device)
         self.titers = titers
+        # train_ffwm.py --crop (models/ffwm_model.py:43): every LightCNN input of the step is the centre-face crop
+        self.crop = bool(crop)
         # data parallelism is live when there are several ranks (force_collectives: also in a one-rank process group -- the
         # one-GPU box's way to run RCCL calls through the capture path)
         self.dp_active = world_size > 1 or bool(force_collectives)
@@ -394,10 +396,26 @@ class FFWMTrainer(object):
             total = total + w * (fx[k] - fy[k]).abs().reshape(n, -1).mean(1)      # the L1 mean of each pair
         return total
 
+    def _light_input(self, x):
+        """LightCNN's input of one image batch: the channel mean, or with crop the centre-face crop (losses.IdentityLoss)."""
+        if not self.crop:
+            return x.mean(1, keepdim=True)
+        from .losses import identity_network_input
+        return identity_network_input(x, True)
+
+    def _light_inputs(self, uniq):
+        """cat of the inputs of several image batches; with crop on the GPU each launch writes its batch slice of the one buffer."""
+        if not self.crop:
+            return torch.cat([u.mean(1, keepdim=True) for u in uniq], 0)
+        if all(u.is_cuda and u.dtype == torch.float32 for u in uniq):
+            from .external_function import identity_input_many
+            return identity_input_many(uniq, True)
+        return torch.cat([self._light_input(u) for u in uniq], 0)
+
     def identity(self, out, gt):
-        _, fc_o, pool_o = self.lightCNN(out.mean(1, keepdim=True))
+        _, fc_o, pool_o = self.lightCNN(self._light_input(out))
         with torch.no_grad():
-            _, fc_g, pool_g = self.lightCNN(gt.mean(1, keepdim=True))
+            _, fc_g, pool_g = self.lightCNN(self._light_input(gt))
         return F.l1_loss(fc_o, fc_g) + F.l1_loss(pool_o, pool_g)
 
     def identity_many(self, outs, gt, weights):
@@ -414,9 +432,9 @@ class FFWMTrainer(object):
                 uniq.append(o)
                 wsum.append(w)
         with torch.no_grad():
-            _, fc_g, pool_g = self.lightCNN(gt.mean(1, keepdim=True))
+            _, fc_g, pool_g = self.lightCNN(self._light_input(gt))
         n, b = len(uniq), gt.size(0)
-        _, fc_o, pool_o = self.lightCNN(torch.cat([u.mean(1, keepdim=True) for u in uniq], 0))
+        _, fc_o, pool_o = self.lightCNN(self._light_inputs(uniq))
         total = 0
         for i, w in enumerate(wsum):
             sl = slice(i * b, (i + 1) * b)
@@ -479,7 +497,7 @@ class FFWMTrainer(object):
                     self._tgt["vgg64"] = self.vgg(F.interpolate(img_F, (64, 64), mode="bilinear") * F.interpolate(mask_F, (64, 64), mode="nearest"))
                 self.loss_streams[1].wait_stream(cur)
                 with torch.cuda.stream(self.loss_streams[1]), torch.no_grad():
-                    self._tgt["light"] = self.lightCNN(img_F.mean(1, keepdim=True))
+                    self._tgt["light"] = self.lightCNN(self._light_input(img_F))
 
             def flows_ready():
                 # called by netG once its encoder is issued: join the flow nets, warp the images, hand the flows over
@@ -599,8 +617,8 @@ class FFWMTrainer(object):
                 _, fc_g, pool_g = pre["light"]
             else:
                 with torch.no_grad():
-                    _, fc_g, pool_g = self.lightCNN(img_F.mean(1, keepdim=True))
-            _, fc_o, pool_o = self.lightCNN(torch.cat([u.mean(1, keepdim=True) for u in uniq], 0))
+                    _, fc_g, pool_g = self.lightCNN(self._light_input(img_F))
+            _, fc_o, pool_o = self.lightCNN(self._light_inputs(uniq))
             side_terms.append((fc_o, fc_g, None, [(i * B, 0, B, w, IDEN) for i, w in enumerate(wsum)]))
             side_terms.append((pool_o, pool_g, None, [(i * B, 0, B, w, IDEN) for i, w in enumerate(wsum)]))
         t128 = vgg_pair(gf128, img_F, mask_F, "vgg128")
@@ -1083,9 +1101,9 @@ class FFWMTrainer(object):
 
     @torch.no_grad()
     def identity_feature(self, fake_F128):
-        """FFWMModel.test (ffwm_model.py:191-202, crop=False): the LightCNN feature used for rank-1 matching."""
+        """FFWMModel.test (ffwm_model.py:191-202) with the trainer's `crop` as opt.crop: the LightCNN feature used for rank-1 matching."""
         self._no_eager_while_captured("identity_feature")
-        _, fea, _ = self.lightCNN(torch.mean(fake_F128, dim=(1,), keepdim=True))
+        _, fea, _ = self.lightCNN(self._light_input(fake_F128))
         return fea
 
 

@@ -635,6 +635,14 @@ int ffwm_mfm_tail_forward(const void* h, const void* bias, const void* residual,
  * division).  crop 1 (H = W = 128 only): mean -> WarpNet(build_grid(B, 98)) -> bilinear resize to 128 x 128 (models/losses.py:85-112)
  * as one 16-tap gather per output pixel. */
 int ffwm_identity_input(const void* img, void* out, int64_t B, int64_t Cin, int64_t H, int64_t W, int crop, int dtype, void* stream);
+/* The adjoint of ffwm_identity_input: grad_out [B, 1, H, W] -> grad_img [B, Cin, H, W], OVERWRITTEN (every element written exactly
+ * once; no zero-fill needed).  crop 0: grad_out / Cin into every channel.  crop 1 (H = W = 128 only): the forward is the separable
+ * linear map out = A_y gray A_x^T (A = resize x sample per axis, from the forward's own coordinates), so grad_img[b, c] =
+ * A_y^T grad_out[b, 0] A_x / Cin, as a gather over the few outputs that touch each input cell, summed in ascending output order:
+ * no atomics, bit-identical from run to run, exactly 0 in rows 0 .. 26 and 127 and columns 0 .. 13 and 114 .. 127 (no tap of the
+ * forward reaches them).  Same argument checks as ffwm_identity_input. */
+int ffwm_identity_input_backward(const void* grad_out, void* grad_img, int64_t B, int64_t Cin, int64_t H, int64_t W, int crop, int dtype,
+                                 void* stream);
 /* torch.cosine_similarity (eps 1e-8 on each norm) of probe [B, D] against gallery [G, D] and its k best per probe: values [B, k]
  * float32 descending, indices [B, k] int32; equal similarities: the lower index first; a NaN similarity ranks above everything.
  * 1 <= k <= min(G, 32), D <= 1024, B <= 65535.  Deterministic, no atomics.  workspace: 16-byte aligned, at least

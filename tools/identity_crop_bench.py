@@ -1,0 +1,183 @@
+"""What training with --crop costs, measured two ways in ONE process, alternating:
+
+    python tools/identity_crop_bench.py [--pairs 5] [--batch 8] [--out profiles/identity_crop_train.txt]
+
+(1) The identity input stage of one train step -- three forward crops (the ground truth under no_grad, fake128 and the guided-filter
+    output) and two backward -- as device time inside a captured graph (launches this small time the host's dispatch when they are
+    issued eagerly): (A) ATen's composition, identity_eval.torch_identity_input under autograd (mean, grid_sample, interpolate and
+    their backward nodes), against (B) the kernels of csrc/lightcnn_eval.hip behind external_function.IdentityInputFunction /
+    identity_input_many.  Each leg is `calls` stages captured into one graph, the replay timed with device events; the legs alternate
+    A / B for --pairs pairs and are reported as median and min-max.
+(2) The captured train step (FFWMTrainer.capture, one hipGraph) of two trainers of one seed, crop=False and crop=True, replayed in
+    alternating windows of --steps steps, reported the same way.
+GPU only: without a device the tool fails.
+"""
+import argparse
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+
+DEV = "cuda:0"
+
+
+def captured(stage, calls):
+    """`calls` runs of stage() in one graph -> a function that replays it and returns device ms per run."""
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(3):
+            stage()
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(calls):
+            stage()
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def replay(reps=5):
+        times = []
+        for _ in range(reps + 1):
+            start.record()
+            g.replay()
+            stop.record()
+            stop.synchronize()
+            times.append(start.elapsed_time(stop) / calls)
+        return statistics.median(times[1:])
+    return replay
+
+
+def kernel_count(fn):
+    """Device kernels of one fn() as torch's profiler sees them (None when it is not available)."""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        return sum(e.count for e in prof.key_averages() if getattr(e, "device_time_total", 0) > 0 or getattr(e, "cuda_time_total", 0) > 0)
+    except Exception:          # noqa: BLE001  (a count is a remark in the report, never a reason to lose the timings)
+        return None
+
+
+def line(name, vals, unit, scale=1.0):
+    return "%s  median %.3f %s  min %.3f  max %.3f  runs [%s]" % (name, scale * statistics.median(vals), unit, scale * min(vals),
+                                                                  scale * max(vals), ", ".join("%.3f" % (scale * v) for v in vals))
+
+
+def verdict(a, b, what_b):
+    margin, worst = statistics.median(a) - statistics.median(b), max(max(a) - min(a), max(b) - min(b))
+    if margin > worst:
+        return margin, worst, "%s is faster beyond the spread" % what_b
+    return margin, worst, ("%s is not slower beyond the spread" % what_b if margin >= -worst else "%s is SLOWER beyond the spread" % what_b)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pairs", type=int, default=5)
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--calls", type=int, default=20, help="input stages per captured graph")
+    ap.add_argument("--steps", type=int, default=10, help="train steps per timed window")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "identity_crop_train.txt"))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("identity_crop_bench: needs an MI355X; a CPU run measures nothing")
+    if args.pairs < 5:
+        sys.exit("identity_crop_bench: at least five pairs")
+
+    from ffwm_amd import trainer
+    from ffwm_amd.external_function import IdentityInputFunction, identity_input_many
+    from ffwm_amd.identity_eval import torch_identity_input
+
+    lines = []
+
+    def out(s=""):
+        print(s, flush=True)
+        lines.append(s)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+    B = args.batch
+    out("# training with --crop at batch %d, 128 x 128, float32, device %s" % (B, torch.cuda.get_device_name(0)))
+    gen = torch.Generator().manual_seed(1)
+    gt = torch.rand(B, 3, 128, 128, generator=gen).to(DEV)
+    fake = torch.rand(B, 3, 128, 128, generator=gen).to(DEV).requires_grad_(True)
+    gf = torch.rand(B, 3, 128, 128, generator=gen).to(DEV).requires_grad_(True)
+    gy = torch.randn(2 * B, 1, 128, 128, generator=gen).to(DEV)
+    keep = {}          # results only, never a tensor with its autograd graph: a graph that stays alive keeps the leaves' gradient
+    # accumulators, which run on the stream they were made on -- the default stream of the eager runs below would enter the capture
+
+    def stage_a():
+        with torch.no_grad():
+            keep["gt"] = torch_identity_input(gt, True)
+        y = torch.cat([torch_identity_input(u, True) for u in (fake, gf)], 0)
+        keep["y"], keep["g"] = y.detach(), torch.autograd.grad(y, (fake, gf), gy)
+
+    def stage_b():
+        with torch.no_grad():
+            keep["gt"] = IdentityInputFunction.apply(gt, True)
+        y = identity_input_many([fake, gf], True)
+        keep["y"], keep["g"] = y.detach(), torch.autograd.grad(y, (fake, gf), gy)
+
+    stage_a()
+    ya, ga = keep["y"].clone(), [g.clone() for g in keep["g"]]
+    stage_b()
+    out("# (1) the input stage of one step: 3 forward crops (one under no_grad) + 2 backward; A = ATen's composition under autograd, "
+        "B = the kernels; %d stages per captured graph, median of 5 replays per run, %d alternating pairs" % (args.calls, args.pairs))
+    out("stage outputs: max |A - B| forward %.3e, gradient %.3e (max |gradient| %.3e)" % (
+        (ya - keep["y"]).abs().max().item(), max((a - b).abs().max().item() for a, b in zip(ga, keep["g"])),
+        max(a.abs().max().item() for a in ga)))
+    ra, rb = captured(stage_a, args.calls), captured(stage_b, args.calls)
+    ms = {"A": [], "B": []}
+    for _ in range(args.pairs):
+        ms["A"].append(ra())
+        ms["B"].append(rb())
+    out(line("input stage  A (ATen composition)", ms["A"], "us", 1e3))
+    out(line("input stage  B (kernels)         ", ms["B"], "us", 1e3))
+    margin, worst, text = verdict(ms["A"], ms["B"], "B")
+    out("input stage  A - B = %.3f us against the larger min-max spread %.3f us: %s; A / B = %.2f" % (
+        1e3 * margin, 1e3 * worst, text, statistics.median(ms["A"]) / statistics.median(ms["B"])))
+    na, nb = kernel_count(stage_a), kernel_count(stage_b)
+    out("input stage  device kernels of one eager stage (profiler): A %s, B %s" % (
+        na if na is not None else "not measured", nb if nb is not None else "not measured"))
+    del ra, rb
+
+    # (2) the captured train step
+    batch = trainer.synthetic_batch(B, DEV, seed=1)
+    trainers = {}
+    for crop in (False, True):
+        t = trainer.FFWMTrainer(DEV, seed=0, capturable=True, crop=crop)
+        t.capture(batch, warmup=3)
+        trainers[crop] = t
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def window(t):
+        t.step(batch)
+        torch.cuda.synchronize()
+        start.record()
+        for _ in range(args.steps):
+            t.step(batch)
+        stop.record()
+        stop.synchronize()
+        return start.elapsed_time(stop) / args.steps
+    step = {False: [], True: []}
+    for _ in range(args.pairs):
+        for crop in (False, True):
+            step[crop].append(window(trainers[crop]))
+    out("# (2) the captured train step (one hipGraph), two trainers of one seed, %d steps per window, %d alternating pairs" % (
+        args.steps, args.pairs))
+    out(line("train step  crop=False", step[False], "ms"))
+    out(line("train step  crop=True ", step[True], "ms"))
+    margin, worst, _ = verdict(step[True], step[False], "crop=False")
+    out("train step  crop=True - crop=False = %.3f ms against the larger min-max spread %.3f ms: %s" % (
+        margin, worst, "the crop costs more than the spread shows" if margin > worst else "the difference is inside the spread"))
+    losses = {crop: {k: float(v) for k, v in trainers[crop].losses.items()} for crop in (False, True)}
+    out("train step  last iden: crop=False %.6g, crop=True %.6g" % (losses[False]["iden"], losses[True]["iden"]))
+
+
+if __name__ == "__main__":
+    main()
