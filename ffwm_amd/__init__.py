@@ -4,7 +4,10 @@ csyxwei/FFWM: hand-written HIP kernels behind the reference's own operator API.
     ffwm_amd.external_function   BlockExtractor / LocalAttnReshape / Resample2d (+Function.apply),
                                  WarpNet, WarpFlipCat, IdentityInputFunction (the identity network's input, --crop included)
     ffwm_amd.losses              the reference's callers restated: AffineRegularizationLoss, PerceptualCorrectness,
-                                 IdentityLoss(lightcnn, crop) -- trainer.FFWMTrainer(..., crop=True) trains against the cropped face
+                                 IdentityLoss(lightcnn, crop) -- trainer.FFWMTrainer(..., crop=True) trains against the cropped face;
+                                 MultiScaleLDLoss / LandmarkLoss(fused=True): all scales and their flow gradients in one call
+    ffwm_amd.trainer             FFWMTrainer (train_ffwm.py; load_pretrained_flow takes --flownetf / --flownetb) and FlowNetTrainer
+                                 (train_flow.py, reverse=True is --reverse; save_networks writes <epoch>_net_flowNet.pth)
     ffwm_amd.compat              block_extractor_cuda / local_attn_reshape_cuda / resample2d_cuda shims
     ffwm_amd.ops                 tensor-level calls into the C ABI (include/ffwm_hip.h)
     ffwm_amd.build               hipcc build recipe for ffwm_amd/lib/libffwm_hip.so

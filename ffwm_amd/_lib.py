@@ -72,6 +72,9 @@ _SIGNATURES = {
     "ffwm_correlation_colmax": [_p, _p, _p, _i64, _i64, _i64, _i, _p],
     "ffwm_correlation_colmax_split": [_p, _p, _p, _i64, _i64, _i64, _i, _p],
     "ffwm_sampling_correctness": [_p] * 9 + [_i64] * 6 + [ctypes.c_double, ctypes.c_double, _i, _p],
+    # (host arrays: flows, grads, sides, divisors, weights; n_scales; lm_S, lm_F, gate, out, skipped, workspace; B, L, dtype, stream)
+    "ffwm_landmark_loss": [_p, _p, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double), _i] + [_p] * 6
+                          + [_i64, _i64, _i, _p],
     "ffwm_guided_filter_backward": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i, _i, _p],
     "ffwm_guided_filter_forward_general": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, ctypes.c_double, _i, _p],
     "ffwm_guided_filter_backward_general": [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, _i, _p],
@@ -99,7 +102,8 @@ _SIGNATURES = {
 
 EXPORTS = sorted(list(_SIGNATURES) + ["ffwm_last_error", "ffwm_conv3x3_winograd_workspace_bytes", "ffwm_conv3x3_winograd_splits",
                                       "ffwm_conv2d_forward_workspace", "ffwm_guided_filter_workspace_bytes",
-                                      "ffwm_sampling_correctness_workspace_bytes", "ffwm_cosine_topk_workspace_bytes",
+                                      "ffwm_sampling_correctness_workspace_bytes", "ffwm_landmark_loss_workspace_bytes",
+                                      "ffwm_cosine_topk_workspace_bytes",
                                       "ffwm_conv3x3_wg_weights_bytes", "ffwm_conv3x3_wg_workspace_bytes"])
 
 
@@ -131,6 +135,8 @@ def load():
     lib.ffwm_guided_filter_workspace_bytes.restype = _i64
     lib.ffwm_sampling_correctness_workspace_bytes.argtypes = [_i64, _i64, _i64, _i]
     lib.ffwm_sampling_correctness_workspace_bytes.restype = _i64
+    lib.ffwm_landmark_loss_workspace_bytes.argtypes = [ctypes.POINTER(_i64), _i, _i64, _i64, _i]
+    lib.ffwm_landmark_loss_workspace_bytes.restype = _i64
     lib.ffwm_cosine_topk_workspace_bytes.argtypes = [_i64] * 4
     lib.ffwm_cosine_topk_workspace_bytes.restype = _i64
     lib.ffwm_conv3x3_wg_weights_bytes.argtypes = [_i64, _i64]

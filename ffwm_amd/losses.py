@@ -55,6 +55,40 @@ class _FusedSamplingCorrectness(Function):
         return (grad * (grad_output / out[1]), None, None, None, None, None)
 
 
+class _FusedLandmarks(Function):
+    """The landmark loss of all scales and d(loss)/d(flow) of every flow that needs one, from one call (csrc/landmark_loss.hip);
+    the landmarks and the gate get no gradient.  `owner.skipped` receives the call's device counter."""
+
+    @staticmethod
+    def forward(ctx, lm_S, lm_F, gate, divisors, weights, owner, *flows):
+        ctx.wants = tuple(ctx.needs_input_grad[6:])
+        out, grads, skipped = ops.landmark_loss([f.contiguous() for f in flows], lm_S, lm_F, gate.contiguous(), divisors, weights, ctx.wants)
+        owner.skipped = skipped
+        ctx.save_for_backward(*[g for g in grads if g is not None])
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        saved = iter(ctx.saved_tensors)
+        return (None,) * 6 + tuple(next(saved) * grad_output if want else None for want in ctx.wants)
+
+
+def _landmarks_take_kernel(flows, lm_S, lm_F, gate):
+    """The fused kernel serves 1 .. 4 square float32 / float64 flows of one batch with int64 landmarks and a gate of the flows'
+    dtype, all on the GPU, when the gate wants no gradient."""
+    if not 1 <= len(flows) <= 4:
+        return False
+    first = flows[0]
+    if first.dtype not in (torch.float32, torch.float64) or gate.requires_grad:
+        return False
+    if not (lm_S.is_cuda and lm_F.is_cuda and gate.is_cuda and lm_S.dtype == torch.int64 and lm_F.dtype == torch.int64):
+        return False
+    if gate.dtype != first.dtype or lm_S.dim() != 3 or lm_S.numel() == 0 or lm_S.shape != lm_F.shape or gate.shape != lm_S.shape:
+        return False
+    return all(f.is_cuda and f.dtype == first.dtype and f.dim() == 4 and f.shape[0] == lm_S.shape[0] and f.shape[1] == 2
+               and f.shape[2] == f.shape[3] and f.shape[2] > 0 for f in flows)
+
+
 def affine_residual_kernels(kz):
     """The kz^2 filters [kz^2, 1, kz, kz] (float64) whose responses, dotted with a window of the sampling grid, give the squared
     distance of that window from the nearest affine map (what losses.py:192-199 builds).  With the design matrix D of the window's
@@ -148,9 +182,19 @@ class MultiAffineRegularizationLoss(nn.Module):
 # The other two losses of FlowNet pre-training (models/flownet_model.py:64-72)
 class LandmarkLoss(nn.Module):
     """MSE between the flow sampled at the frontal landmarks and the (normalised) profile landmarks
-    (losses.py:61-74).  flow [B,2,s,s]; lm_S / lm_F integer pixel coordinates [B,L,2]; gate [B,L,2]."""
+    (losses.py:61-74).  flow [B,2,s,s]; lm_S / lm_F integer pixel coordinates [B,L,2]; gate [B,L,2].
+    ``fused=True``: loss and gradient from one call of csrc/landmark_loss.hip wherever it applies (GPU tensors, a float32 /
+    float64 flow); a landmark outside the plane is then skipped and counted in ``.skipped`` (a device int32 scalar, the last
+    call's) where ``gather`` would raise a device assert.  Everywhere else the composition below, unchanged."""
+
+    def __init__(self, fused=False):
+        super().__init__()
+        self.fused = fused
+        self.skipped = None
 
     def forward(self, flow, lm_S, lm_F, gate):
+        if self.fused and _landmarks_take_kernel([flow], lm_S, lm_F, gate):
+            return _FusedLandmarks.apply(lm_S, lm_F, gate, (1,), (1.0,), self, flow)
         side = flow.size(-1)
         # the flow vectors at the frontal landmarks: pixel (x, y) of the row-major plane is element y * side + x
         cell = (lm_F[..., 1] * side + lm_F[..., 0]).unsqueeze(1).expand(-1, 2, -1)             # [B, 2, L]
@@ -163,15 +207,23 @@ class MultiScaleLDLoss(nn.Module):
     """losses.py:114-126: LandmarkLoss on the 128 / 64 / 32 px flows, weights 1000 / 1000 / 1500.  The integer
     landmarks are divided by the scale with INTEGER division: that is what ``lm.div(scale)`` did for integer
     tensors in the reference's pinned PyTorch 1.5.0 (README.md:14); from 1.6 on ``div`` is true division and
-    the reference's own ``torch.gather`` call rejects the float index."""
+    the reference's own ``torch.gather`` call rejects the float index.
+    ``fused=True``: ONE call of csrc/landmark_loss.hip for the three scales (divisors 128 // s) wherever it applies, see
+    LandmarkLoss; the gradients of the flows come without float atomics, so two runs agree bit for bit."""
 
-    def __init__(self):
+    def __init__(self, fused=False):
         super().__init__()
         self.criterionLD = LandmarkLoss()
         self.weights = [1000, 1000, 1500]
         self.img_size = 128
+        self.fused = fused
+        self.skipped = None          # the device counter of the last fused call; nothing in a step reads it back
 
     def forward(self, flows, lm_S, lm_F, gate):
+        if self.fused and len(flows) <= len(self.weights) and _landmarks_take_kernel(flows, lm_S, lm_F, gate) \
+                and all(0 < f.size(3) <= self.img_size for f in flows):
+            divisors = tuple(self.img_size // f.size(3) for f in flows)
+            return _FusedLandmarks.apply(lm_S, lm_F, gate, divisors, tuple(float(w) for w in self.weights[:len(flows)]), self, *flows)
         ld_loss = 0
         for i, flow in enumerate(flows):
             scale = self.img_size // flow.size(3)

@@ -541,6 +541,72 @@ def sampling_correctness(source, target, flow, corr_max, mask, eps, want_grad, w
     return out, grad, loss_map
 
 
+# ---------------------------------------------------------------- fused landmark loss
+def landmark_loss(flows, lm_S, lm_F, gate, divisors, weights, want_grad, out_grads=None):
+    """-> (out[n + 1], grads, skipped): LandmarkLoss on n = 1 .. 4 flow scales of one batch in one call (csrc/landmark_loss.hip).
+    flows[i] [B,2,s,s]; lm_S, lm_F int64 [B,L,2] in (x, y) order; gate [B,L,2] in the flows' dtype; divisors[i] >= 1 the integer the
+    landmarks are floor-divided by on scale i; weights[i] its weight.  out[0] = sum_i weights[i] * mse_i, out[1 + i] = mse_i.
+    want_grad: a bool, or one per scale; grads[i] = weights[i] * d(mse_i)/d(flows[i]) (None where not wanted), every element
+    written (out_grads[i], where given, is the destination: contiguous, of the flow's shape; nobody needs to zero-fill it).
+    skipped: a device int32 scalar, the landmarks with an lm_F component outside the plane of one scale or more; they add nothing
+    to the loss or the gradient of that scale and are never dereferenced."""
+    name = "landmark_loss"
+    flows = list(flows)
+    n = len(flows)
+    if not 1 <= n <= 4 or len(divisors) != n or len(weights) != n:
+        raise ValueError("%s: need 1 .. 4 flows with one divisor and one weight each" % name)
+    wants = [bool(want_grad)] * n if isinstance(want_grad, (bool, int)) else [bool(w) for w in want_grad]
+    if len(wants) != n:
+        raise ValueError("%s: want_grad must be a bool or one per scale" % name)
+    B = flows[0].shape[0] if flows[0].dim() == 4 else -1
+    for f in flows:
+        if f.dim() != 4 or f.shape[0] != B or f.shape[1] != 2 or f.shape[2] != f.shape[3]:
+            raise ValueError("%s: every flow must be a square [B,2,s,s] of one batch size, got %s" % (name, tuple(f.shape)))
+    if lm_S.dim() != 3 or lm_S.shape[0] != B or lm_S.shape[2] != 2 or lm_F.shape != lm_S.shape or gate.shape != lm_S.shape:
+        raise ValueError("%s: lm_S, lm_F and gate must all be [B,L,2] with the flows' B, got %s, %s, %s"
+                         % (name, tuple(lm_S.shape), tuple(lm_F.shape), tuple(gate.shape)))
+    L = lm_S.shape[1]
+    if B == 0 or L == 0 or any(f.shape[2] == 0 for f in flows):
+        raise ValueError("%s: B, L and the sides must be positive (the mean of nothing)" % name)
+    divisors = [int(q) for q in divisors]
+    if any(q < 1 for q in divisors):
+        raise ValueError("%s: divisors must be integers >= 1" % name)
+    _check(name, *flows)
+    for t, what in ((lm_S, "lm_S"), (lm_F, "lm_F"), (gate, "gate")):
+        if not t.is_cuda:
+            raise NotImplementedError("%s: ffwm_amd ops run on the GPU only (got a %s tensor)" % (name, t.device))
+        if t.device != flows[0].device:
+            raise ValueError("%s: %s must live on the flows' device" % (name, what))
+    if lm_S.dtype != torch.int64 or lm_F.dtype != torch.int64:
+        raise TypeError("%s: lm_S and lm_F must be int64 tensors" % name)
+    if gate.dtype != flows[0].dtype:
+        raise TypeError("%s: gate must have the flows' dtype (%s vs %s)" % (name, gate.dtype, flows[0].dtype))
+    lm_S, lm_F, gate = lm_S.contiguous(), lm_F.contiguous(), gate.contiguous()
+    code = _dtype_code(flows[0])
+    grads = []
+    for i, f in enumerate(flows):
+        g = None
+        if wants[i]:
+            g = out_grads[i] if out_grads is not None and out_grads[i] is not None else torch.empty_like(f)
+            if g.shape != f.shape or g.dtype != f.dtype or g.device != f.device or not g.is_contiguous():
+                raise ValueError("%s: a gradient destination must be a contiguous tensor of its flow's shape, dtype and device" % name)
+        grads.append(g)
+    out = flows[0].new_empty(n + 1)
+    skipped = torch.empty((), dtype=torch.int32, device=flows[0].device)
+    lib = _lib.load()
+    sides = (ctypes.c_int64 * n)(*[f.shape[2] for f in flows])
+    nbytes = lib.ffwm_landmark_loss_workspace_bytes(sides, n, B, L, code)
+    _lib.check(min(nbytes, 0), "ffwm_landmark_loss_workspace_bytes")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=flows[0].device)
+    fl = (ctypes.c_void_p * n)(*[_ptr(f) for f in flows])
+    gr = (ctypes.c_void_p * n)(*[_ptr(g) for g in grads])
+    with _on_device(flows[0]) as stream:
+        _lib.check(lib.ffwm_landmark_loss(fl, gr, sides, (ctypes.c_int64 * n)(*divisors), (ctypes.c_double * n)(*[float(w) for w in weights]),
+                                          n, _ptr(lm_S), _ptr(lm_F), _ptr(gate), _ptr(out), _ptr(skipped), _ptr(ws), B, L, code, stream),
+                   "ffwm_landmark_loss")
+    return out, grads, skipped
+
+
 # ---------------------------------------------------------------- conv weight gradient (MFMA)
 def conv3x3_wgrad_supported(input, grad_output):
     """Shapes the MFMA weight-gradient kernel takes: float32 NCHW, W a multiple of 64, below 4 GiB."""

@@ -146,6 +146,14 @@ class _FlowGate(torch.autograd.Function):
         return (None, None) + tuple(grads)
 
 
+def _load_state_file(net, path, device):
+    """net.load_state_dict of a state-dict file, as BaseModel.load_networks reads one (models/base_model.py:207-229)."""
+    sd = torch.load(path, map_location=str(device))
+    if hasattr(sd, "_metadata"):
+        del sd._metadata
+    net.load_state_dict(sd)
+
+
 class FFWMTrainer(object):
     def __init__(self, device, world_size=1, seed=0, titers=0, bucket_bytes=64 << 20, warp=None,
                  warp_flipcat=None, ngf=64, capturable=False, fused_spectral_norm=None, batched_losses=True,
@@ -1078,6 +1086,15 @@ class FFWMTrainer(object):
                 del sd._metadata
             getattr(self, name).load_state_dict(sd)
 
+    def load_pretrained_flow(self, flownetf=None, flownetb=None):
+        """--flownetf / --flownetb of train_ffwm.py (models/ffwm_model.py:34-35): each argument is the path of a
+        '<epoch>_net_flowNet.pth' that FlowNet pre-training wrote (FlowNetTrainer.save_networks; --reverse for flowNetB), loaded
+        into flowNetF / flowNetB; None leaves that network as it is."""
+        self._no_eager_while_captured("load_pretrained_flow")
+        for path, name in ((flownetf, "flowNetF"), (flownetb, "flowNetB")):
+            if path is not None:
+                _load_state_file(getattr(self, name), path, self.device)
+
     def _no_eager_while_captured(self, what):
         """Vendor convolutions issued eagerly between replays of a captured step made the replays read freed memory (measured in
         round 3; not root-caused: MIOpen's workspaces of the eager calls and the graph's private pool meet
@@ -1116,10 +1133,17 @@ class FlowNetTrainer(object):
         Adam(lr 4e-4, betas (0.5, 0.999)) on flowNet
     This is the only training path of the reference that runs the custom ops.  Here the warp of
     the VGG features and of the image go through the HIP warp kernels and the regulariser is the fused
-    affine-regularisation kernel.  VGG19 is seeded random (no pretrained weights offline), frozen."""
+    affine-regularisation kernel.  VGG19 is seeded random (no pretrained weights offline), frozen.
+
+    ``reverse=True`` is train_flow.py --reverse (flownet_model.py:41-46,58-62), the run that produces flowNetB: the network still
+    reads the profile b["img_S"], but it learns the flow that warps the FRONTAL image onto the profile -- the two images, the two
+    landmark sets and the mask change places in the warp and in the losses.  save_networks / load_networks write and read the
+    reference's one file '<epoch>_net_flowNet.pth', which FFWMTrainer.load_pretrained_flow takes as --flownetf / --flownetb."""
+
+    MODEL_NAMES = ("flowNet",)      # flownet_model.py:24
 
     def __init__(self, device, world_size=1, seed=0, ngf=64, warp=None, fused_regularization=None, bucket_bytes=64 << 20,
-                 routed=None, capturable=False, fused_correctness=False, corr_precision="fp32"):
+                 routed=None, capturable=False, fused_correctness=False, corr_precision="fp32", fused_landmarks=False, reverse=False):
         from .losses import MultiAffineRegularizationLoss, MultiScaleLDLoss, PerceptualCorrectness
         self.device = torch.device(device)
         torch.manual_seed(seed)
@@ -1144,7 +1168,10 @@ class FlowNetTrainer(object):
         # corr_precision: "bf16x3" takes the correlation maximum of that loss on the bf16 MFMA kernel (csrc/correlation.hip); fp32 by default
         self.Correctness = PerceptualCorrectness(self.vgg, self.warp, fused=bool(fused_correctness) and self.device.type == "cuda",
                                                  corr_precision=corr_precision)
-        self.criterionLD = MultiScaleLDLoss()
+        # fused_landmarks: the three scales of the landmark loss and their flow gradients as one call without float atomics
+        # (csrc/landmark_loss.hip) instead of the gather / mse composition; off by default
+        self.criterionLD = MultiScaleLDLoss(fused=bool(fused_landmarks) and self.device.type == "cuda")
+        self.reverse = bool(reverse)
         # the same routes FFWMTrainer gives its flow nets (round 3): Winograd forward / data gradient, conv_fwd.hip for the stride-2 /
         # transposed / small-plane layers, direct kernels for the two-channel layers, tiled weight gradients, fused BatchNorm + LeakyReLU
         if routed is None:
@@ -1173,12 +1200,15 @@ class FlowNetTrainer(object):
         if self.device.type == "cuda" and _GRAD_ARENA_ON:
             conv.GRAD_ARENA.begin(self.device)
         gate = torch.cat((b["gate"], b["gate"]), 2)
-        flow, flow64, flow32 = self.flowNet(b["img_S"])
-        self.fake_F = self.warp(b["img_S"], flow)
+        flow, flow64, flow32 = self.flowNet(b["img_S"])          # the profile, in both directions (flownet_model.py:58-61)
+        # --reverse swaps the roles of the two views everywhere but at the network's input (flownet_model.py:41-46)
+        src, tgt = ("img_F", "img_S") if self.reverse else ("img_S", "img_F")
+        lm_src, lm_tgt = ("lm_F", "lm_S") if self.reverse else ("lm_S", "lm_F")
+        self.fake_F = self.warp(b[src], flow)
         flows = [flow, flow64, flow32]
-        loss_cor = self.Correctness(b["img_F"], b["img_S"], flows[::-1], [2, 1, 0], norm_mask=b["mask_F"]) * 20
+        loss_cor = self.Correctness(b[tgt], b[src], flows[::-1], [2, 1, 0], norm_mask=b["mask_S" if self.reverse else "mask_F"]) * 20
         loss_reg = self.Regularization(flows[::-1]) * 0.01
-        loss_lm = self.criterionLD(flows, b["lm_S"], b["lm_F"], gate)
+        loss_lm = self.criterionLD(flows, b[lm_src], b[lm_tgt], gate)
         loss = loss_cor + loss_lm + loss_reg
         self.reducer.zero_grad()
         try:
@@ -1263,3 +1293,19 @@ class FlowNetTrainer(object):
 
     def loss_values(self):
         return {k: float(v.detach()) for k, v in self.losses.items()}
+
+    def save_networks(self, save_dir, epoch):
+        """BaseModel.save_networks (models/base_model.py:172-191) for the one network of this model: '<epoch>_net_flowNet.pth',
+        CPU tensors, the reference's key names.  Like the reference, optimizer state is not saved."""
+        import os
+        os.makedirs(save_dir, exist_ok=True)
+        for name in self.MODEL_NAMES:
+            sd = {k: v.detach().cpu() for k, v in getattr(self, name).state_dict().items()}
+            torch.save(sd, os.path.join(save_dir, "%s_net_%s.pth" % (epoch, name)))
+
+    def load_networks(self, load_dir, epoch):
+        """BaseModel.load_networks (models/base_model.py:207-229).  The parameters are written in place, so a captured step goes on
+        with the loaded weights."""
+        import os
+        for name in self.MODEL_NAMES:
+            _load_state_file(getattr(self, name), os.path.join(load_dir, "%s_net_%s.pth" % (epoch, name)), self.device)

@@ -20,6 +20,7 @@
  *   ffwm_correlation_colmax         <- max(bmm(source, target), dim=1)  models/losses.py:347-353
  *   ffwm_correlation_colmax_split   <- the same on bf16 MFMA with a hi/lo operand split (opt-in)
  *   ffwm_sampling_correctness       <- PerceptualCorrectness.calculate_loss (warp, cosine, exp, mask, sums)  models/losses.py:341-371
+ *   ffwm_landmark_loss              <- MultiScaleLDLoss / LandmarkLoss, every scale and its gradient in one call  models/losses.py:61-74,114-126
  *   ffwm_block_attention_*          <- avg_pool2d(BlockExtractor * LocalAttnReshape)  (composition of the ops above)
  *   ffwm_spectral_norm_*            <- torch.nn.utils.spectral_norm hooks models/base_networks.py:5,218-264,381-413
  *   ffwm_conv3x3_wgrad[_block]      <- convolution_backward grad_weight / grad_bias of the nn.Conv2d(., ., 3, 1, 1) layers
@@ -344,6 +345,29 @@ int ffwm_sampling_correctness(const void* source, const void* target, const void
                               const void* mask, void* loss_map, void* grad_flow, void* out, void* workspace,
                               int64_t B, int64_t C, int64_t Hi, int64_t Wi, int64_t H, int64_t W, double e1,
                               double eps, int dtype, void* stream);
+
+/* ---- fused landmark loss (FlowNet pre-training) ---------------------------------------------------
+ * LandmarkLoss / MultiScaleLDLoss of models/losses.py:61-74,114-126 for ALL flow scales of one batch (1 <= n_scales <= 4) in one
+ * call, with the gradient for every flow and WITHOUT float atomics (profiler rows `landmark_loss` and `landmark_loss_reduce`, a
+ * one-block launch that adds the per-block sums in a fixed order).  Host arrays of n_scales entries: flows[i] -> [B,2,s_i,s_i],
+ * grads (NULL, or grads[i] -> the same shape or NULL), sides[i] = s_i, divisors[i] = q_i >= 1, weights[i].  Device tensors:
+ * lm_S, lm_F int64 [B,L,2] in (x, y) order, gate [B,L,2] in the flows' dtype, all contiguous.  Per scale, `div` rounding toward
+ * minus infinity (torch.div(..., rounding_mode="floor")):
+ *   (X, Y) = (lm_F[b,l,0] div q, lm_F[b,l,1] div q),    w_c = (lm_S[b,l,c] div q) * (2 / s) - 1
+ *   e[b,l,c] = (flow[b,c,Y,X] - w_c) * gate[b,l,c],     mse = sum e^2 / (2 B L)
+ *   out[1 + i] = mse_i,    out[0] = sum_i weights[i] * mse_i                                   (out: n_scales + 1 elements)
+ *   grads[i][b,c,Y,X] = weights[i] / (B L) * sum over the landmarks of sample b on (X, Y) of gate^2 (flow - w_c); every other
+ *   element is written as 0: the destination is OVERWRITTEN completely with plain stores (one owner per cell), no zero-fill.
+ * A landmark with an lm_F component outside [0, s q) is never dereferenced: it adds 0 to the loss and the gradient of that scale
+ * and still counts in the denominator.  *skipped (a device int32, overwritten) = the landmarks (b, l) that one scale or more
+ * skipped.  lm_S is converted to the dtype before the product: exact below 2^24 (2^53).  Every sum meets in an order fixed by
+ * the shapes (the loss in double, per block into `workspace`: ffwm_landmark_loss_workspace_bytes bytes, 8-byte aligned, contents
+ * irrelevant on entry and exit; a negative ffwm_status for sizes the entry point refuses): two calls agree bit for bit.
+ * Sides up to 4096 with s q < 2^31, B and L up to 2^30; beyond that FFWM_ERR_SIZE. */
+int64_t ffwm_landmark_loss_workspace_bytes(const int64_t* sides, int n_scales, int64_t B, int64_t L, int dtype);
+int ffwm_landmark_loss(const void* const* flows, void* const* grads, const int64_t* sides, const int64_t* divisors,
+                       const double* weights, int n_scales, const void* lm_S, const void* lm_F, const void* gate,
+                       void* out, void* skipped, void* workspace, int64_t B, int64_t L, int dtype, void* stream);
 
 /* Fused extractor + attention consumer (the GFLA-style local attention the cfg-5 shape
  * models): what the reference API can only express as

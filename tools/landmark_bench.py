@@ -1,0 +1,199 @@
+"""What the fused landmark loss (csrc/landmark_loss.hip) buys, measured two ways on an MI355X:
+
+    python tools/landmark_bench.py [--pairs 5] [--out profiles/landmark_loss.txt]
+
+(a) MultiScaleLDLoss forward + backward on flows [B, 2, 128 / 64 / 32, ...] with L = 1024 landmarks, B = 6 and 8, as device time
+    inside a captured graph (launches this small time the host's dispatch when they are issued eagerly): the composition
+    (MultiScaleLDLoss()) against one call of the kernel (MultiScaleLDLoss(fused=True)).  Each leg is `calls` evaluations captured
+    into one graph, the replay timed with device events; the legs alternate for --pairs pairs and are reported as median and
+    min-max, with the profiler's kernel-event count of one eager evaluation of each.
+(b) The captured FlowNetTrainer step at batch 6 of two trainers of one seed, fused_landmarks off and on, replayed in alternating
+    windows of --steps steps, reported the same way.
+Every GPU step -- (a) at B = 6, (a) at B = 8, (b) -- is a child process under its own time limit; the parent never opens the GPU,
+stops at the first step that fails and writes what it has.  GPU only: without a device the tool fails.
+"""
+import argparse
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+DEV = "cuda:0"
+LIMITS = {"a": 240, "b": 420}          # seconds per child
+
+
+def captured(stage, calls):
+    """`calls` runs of stage() in one graph -> a function that replays it and returns device ms per run."""
+    import torch
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(3):
+            stage()
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(calls):
+            stage()
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def replay(reps=5):
+        times = []
+        for _ in range(reps + 1):
+            start.record()
+            g.replay()
+            stop.record()
+            stop.synchronize()
+            times.append(start.elapsed_time(stop) / calls)
+        return statistics.median(times[1:])
+    return replay
+
+
+def kernel_count(fn):
+    """Device kernels of one fn() as torch's profiler sees them (None when it is not available)."""
+    import torch
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        return sum(e.count for e in prof.key_averages() if getattr(e, "device_time_total", 0) > 0 or getattr(e, "cuda_time_total", 0) > 0)
+    except Exception:          # noqa: BLE001  (a count is a remark in the report, never a reason to lose the timings)
+        return None
+
+
+def line(name, vals, unit, scale=1.0):
+    return "%s  median %.3f %s  min %.3f  max %.3f  runs [%s]" % (name, scale * statistics.median(vals), unit, scale * min(vals),
+                                                                  scale * max(vals), ", ".join("%.3f" % (scale * v) for v in vals))
+
+
+def part_a(args):
+    import torch
+    from ffwm_amd import losses, trainer
+    B = args.batch
+    batch = trainer.synthetic_batch(B, DEV, seed=1)
+    gate = torch.cat((batch["gate"], batch["gate"]), 2)
+    gen = torch.Generator().manual_seed(2)
+    flows = [(torch.rand(B, 2, s, s, generator=gen) * 2 - 1).to(DEV).requires_grad_(True) for s in (128, 64, 32)]
+    modules = {"A": losses.MultiScaleLDLoss(), "B": losses.MultiScaleLDLoss(fused=True)}
+    keep = {}          # results only, never a tensor with its autograd graph (it would keep gradient accumulators of the eager stream)
+
+    def stage(which):
+        def run():
+            loss = modules[which](flows, batch["lm_S"], batch["lm_F"], gate)
+            keep["loss"], keep["g"] = loss.detach(), torch.autograd.grad(loss, flows)
+        return run
+
+    stage("A")()
+    la, ga = keep["loss"].clone(), [g.clone() for g in keep["g"]]
+    stage("B")()
+    print("# (a) MultiScaleLDLoss forward + backward, B = %d, L = %d, flows 128 / 64 / 32, float32, device %s" % (
+        B, batch["lm_S"].shape[1], torch.cuda.get_device_name(0)))
+    print("#     A = the composition, B = fused=True; %d evaluations per captured graph, median of 5 replays per run, %d alternating "
+          "pairs" % (args.calls, args.pairs))
+    print("B%d  loss A %.6f  B %.6f;  max |gradient A - B| %.3e (max |gradient| %.3e)" % (
+        B, float(la), float(keep["loss"]), max((a - b).abs().max().item() for a, b in zip(ga, keep["g"])),
+        max(a.abs().max().item() for a in ga)))
+    ra, rb = captured(stage("A"), args.calls), captured(stage("B"), args.calls)
+    ms = {"A": [], "B": []}
+    for _ in range(args.pairs):
+        ms["A"].append(ra())
+        ms["B"].append(rb())
+    print(line("B%d  A (composition)" % B, ms["A"], "us", 1e3))
+    print(line("B%d  B (fused)      " % B, ms["B"], "us", 1e3))
+    margin = statistics.median(ms["A"]) - statistics.median(ms["B"])
+    worst = max(max(ms["A"]) - min(ms["A"]), max(ms["B"]) - min(ms["B"]))
+    print("B%d  A - B = %.3f us against the larger min-max spread %.3f us: the fused call is %s; A / B = %.2f" % (
+        B, 1e3 * margin, 1e3 * worst, "below the composition by more than the spread" if margin > worst else
+        ("NOT below the composition by more than the spread" if margin >= -worst else "SLOWER than the composition beyond the spread"),
+        statistics.median(ms["A"]) / statistics.median(ms["B"])))
+    del ra, rb
+    na, nb = kernel_count(stage("A")), kernel_count(stage("B"))
+    print("B%d  device kernel events of one eager evaluation (profiler): A %s, B %s" % (
+        B, na if na is not None else "not measured", nb if nb is not None else "not measured"), flush=True)
+
+
+def part_b(args):
+    import torch
+    from ffwm_amd import trainer
+    B = 6
+    batch = trainer.synthetic_batch(B, DEV, seed=1)
+    trainers = {}
+    for fused in (False, True):
+        t = trainer.FlowNetTrainer(DEV, seed=0, capturable=True, fused_landmarks=fused)
+        t.capture(batch, warmup=3)
+        trainers[fused] = t
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def window(t):
+        t.step(batch)
+        torch.cuda.synchronize()
+        start.record()
+        for _ in range(args.steps):
+            t.step(batch)
+        stop.record()
+        stop.synchronize()
+        return start.elapsed_time(stop) / args.steps
+    step = {False: [], True: []}
+    for _ in range(args.pairs):
+        for fused in (False, True):
+            step[fused].append(window(trainers[fused]))
+    print("# (b) the captured FlowNetTrainer step (one hipGraph) at batch %d, two trainers of one seed, %d steps per window, %d "
+          "alternating pairs" % (B, args.steps, args.pairs))
+    print(line("step  fused_landmarks=False", step[False], "ms"))
+    print(line("step  fused_landmarks=True ", step[True], "ms"))
+    margin = statistics.median(step[False]) - statistics.median(step[True])
+    worst = max(max(v) - min(v) for v in step.values())
+    print("step  off - on = %.3f ms against the larger min-max spread %.3f ms: %s" % (
+        margin, worst, "the fused step is faster beyond the spread" if margin > worst else
+        ("the difference is inside the spread" if margin >= -worst else "the fused step is SLOWER beyond the spread")))
+    lm = {f: float(trainers[f].losses["lm"]) for f in (False, True)}
+    print("step  last lm: off %.6g, on %.6g" % (lm[False], lm[True]), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pairs", type=int, default=5)
+    ap.add_argument("--calls", type=int, default=20, help="loss evaluations per captured graph")
+    ap.add_argument("--steps", type=int, default=10, help="train steps per timed window")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "landmark_loss.txt"))
+    ap.add_argument("--part", choices=("a", "b"), help="run one GPU step in this process (what the parent starts)")
+    ap.add_argument("--batch", type=int, default=6)
+    args = ap.parse_args()
+    if args.pairs < 5:
+        sys.exit("landmark_bench: at least five pairs")
+    if args.part:
+        import torch
+        if not torch.cuda.is_available():
+            sys.exit("landmark_bench: needs an MI355X; a CPU run measures nothing")
+        return part_a(args) if args.part == "a" else part_b(args)
+
+    lines = []
+    common = [sys.executable, os.path.abspath(__file__), "--pairs", str(args.pairs), "--calls", str(args.calls), "--steps", str(args.steps)]
+    status = 0
+    for extra in (["--part", "a", "--batch", "6"], ["--part", "a", "--batch", "8"], ["--part", "b"]):
+        try:
+            r = subprocess.run(common + extra, capture_output=True, text=True, timeout=LIMITS[extra[1]], cwd=ROOT)
+            text, status = r.stdout, r.returncode
+            if status != 0:
+                text += "landmark_bench: `%s` ended with status %d\n%s\n" % (" ".join(extra), status, r.stderr[-2000:])
+        except subprocess.TimeoutExpired as e:
+            text = (e.stdout.decode() if isinstance(e.stdout, bytes) else e.stdout or "") \
+                + "landmark_bench: `%s` passed its limit of %d s\n" % (" ".join(extra), LIMITS[extra[1]])
+            status = 124
+        print(text, end="", flush=True)
+        lines.append(text)
+        if status != 0:
+            break              # nothing more is started on the GPU after a step that failed
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("".join(lines))
+    sys.exit(status)
+
+
+if __name__ == "__main__":
+    main()
