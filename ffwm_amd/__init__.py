@@ -5,9 +5,13 @@ csyxwei/FFWM: hand-written HIP kernels behind the reference's own operator API.
                                  WarpNet, WarpFlipCat, IdentityInputFunction (the identity network's input, --crop included)
     ffwm_amd.losses              the reference's callers restated: AffineRegularizationLoss, PerceptualCorrectness,
                                  IdentityLoss(lightcnn, crop) -- trainer.FFWMTrainer(..., crop=True) trains against the cropped face;
-                                 MultiScaleLDLoss / LandmarkLoss(fused=True): all scales and their flow gradients in one call
-    ffwm_amd.trainer             FFWMTrainer (train_ffwm.py; load_pretrained_flow takes --flownetf / --flownetb) and FlowNetTrainer
-                                 (train_flow.py, reverse=True is --reverse; save_networks writes <epoch>_net_flowNet.pth)
+                                 MultiScaleLDLoss / LandmarkLoss(fused=True): all scales and their flow gradients in one call;
+                                 ClassifierLoss(fused=True): cross entropy over 79 077 classes, its gradient, prec@1 / prec@5 in one call
+    ffwm_amd.trainer             FFWMTrainer (train_ffwm.py; load_pretrained_flow takes --flownetf / --flownetb, load_lightcnn
+                                 --lightcnn), FlowNetTrainer (train_flow.py, reverse=True is --reverse; save_networks writes
+                                 <epoch>_net_flowNet.pth) and LightCNNTrainer (lightcnn/finetune.py: the reference's parameter groups,
+                                 learning-rate schedule, validation and lightCNN_<n>_checkpoint.pth files)
+    ffwm_amd.optim               FlatAdam and FlatSGD: an optimizer step as one streaming kernel over the reducer's flat arrays
     ffwm_amd.compat              block_extractor_cuda / local_attn_reshape_cuda / resample2d_cuda shims
     ffwm_amd.ops                 tensor-level calls into the C ABI (include/ffwm_hip.h)
     ffwm_amd.build               hipcc build recipe for ffwm_amd/lib/libffwm_hip.so

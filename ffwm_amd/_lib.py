@@ -52,6 +52,11 @@ _SIGNATURES = {
     "ffwm_conv3x3_winograd_forward": [_p, _p, _p, _p, _p] + [_i64] * 5 + [_i, _i, ctypes.c_double, _i, _p],
     "ffwm_adam_step": [_p, _p, _p, _p, _i64] + [ctypes.c_double] * 4 + [_i64, _i, _p],
     "ffwm_adam_step_device": [_p, _p, _p, _p, _i64] + [ctypes.c_double] * 4 + [_p, _i, _p],
+    # (params, grads, momentum_buf, n, seg_end, seg_group, n_seg, group_lr, group_wd, n_groups, momentum, dtype, stream)
+    "ffwm_sgd_step": [_p, _p, _p, _i64, _p, _p, _i, _p, _p, _i, ctypes.c_double, _i, _p],
+    # (logits, target, out, row_loss, rank, grad_logits, skipped, workspace, B, N, dtype, stream)
+    "ffwm_softmax_xent": [_p] * 8 + [_i64, _i64, _i, _p],
+    "ffwm_softmax_xent_chunk": [],
     "ffwm_conv3x3_wgrad": [_p, _p, _p, _p] + [_i64] * 5 + [_i, _p],
     "ffwm_conv3x3_wgrad_block": [_p, _p, _p, _p] + [_i64] * 9 + [_i, _p],
     "ffwm_block_attention_forward": [_p, _p, _p, _p] + [_i64] * 6 + [_i, _i, _p],
@@ -103,7 +108,7 @@ _SIGNATURES = {
 EXPORTS = sorted(list(_SIGNATURES) + ["ffwm_last_error", "ffwm_conv3x3_winograd_workspace_bytes", "ffwm_conv3x3_winograd_splits",
                                       "ffwm_conv2d_forward_workspace", "ffwm_guided_filter_workspace_bytes",
                                       "ffwm_sampling_correctness_workspace_bytes", "ffwm_landmark_loss_workspace_bytes",
-                                      "ffwm_cosine_topk_workspace_bytes",
+                                      "ffwm_cosine_topk_workspace_bytes", "ffwm_softmax_xent_workspace_bytes",
                                       "ffwm_conv3x3_wg_weights_bytes", "ffwm_conv3x3_wg_workspace_bytes"])
 
 
@@ -137,6 +142,8 @@ def load():
     lib.ffwm_sampling_correctness_workspace_bytes.restype = _i64
     lib.ffwm_landmark_loss_workspace_bytes.argtypes = [ctypes.POINTER(_i64), _i, _i64, _i64, _i]
     lib.ffwm_landmark_loss_workspace_bytes.restype = _i64
+    lib.ffwm_softmax_xent_workspace_bytes.argtypes = [_i64, _i64, _i]
+    lib.ffwm_softmax_xent_workspace_bytes.restype = _i64
     lib.ffwm_cosine_topk_workspace_bytes.argtypes = [_i64] * 4
     lib.ffwm_cosine_topk_workspace_bytes.restype = _i64
     lib.ffwm_conv3x3_wg_weights_bytes.argtypes = [_i64, _i64]

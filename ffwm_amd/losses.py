@@ -89,6 +89,57 @@ def _landmarks_take_kernel(flows, lm_S, lm_F, gate):
                and f.shape[2] == f.shape[3] and f.shape[2] > 0 for f in flows)
 
 
+class _FusedClassifier(Function):
+    """Mean cross entropy, d(loss)/d(logits), prec@1 and prec@5 from one call (csrc/softmax_xent.hip); the gradient is kept from the
+    forward call.  `owner` receives prec1, prec5, rank and the device counter of skipped rows."""
+
+    @staticmethod
+    def forward(ctx, logits, target, owner):
+        want = ctx.needs_input_grad[0]
+        out, _, rank, grad, skipped = ops.softmax_xent(logits, target, want_grad=want)
+        owner.prec1, owner.prec5, owner.rank, owner.skipped = out[1], out[2], rank, skipped
+        if want:
+            ctx.save_for_backward(grad)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        if not ctx.saved_tensors:
+            return None, None, None
+        return ctx.saved_tensors[0] * grad_output, None, None
+
+
+def accuracy(output, target, topk=(1,)):
+    """lightcnn/finetune.py:294-307: precision@k in percent, from topk's indices."""
+    maxk = max(topk)
+    pred = output.topk(maxk, 1, True, True)[1].t()
+    correct = pred.eq(target.view(1, -1).expand_as(pred))
+    return [correct[:k].reshape(-1).float().sum(0).mul_(100.0 / target.size(0)) for k in topk]
+
+
+class ClassifierLoss(nn.Module):
+    """nn.CrossEntropyLoss plus accuracy(output, target, (1, 5)) of every step (lightcnn/finetune.py:109,152-159).  forward(logits
+    [B, N], target int64 [B]) -> loss; ``.prec1`` / ``.prec5`` hold the step's precisions as scalars on the logits' device.
+
+    ``fused=True``: loss, gradient and both precisions from one call of csrc/softmax_xent.hip wherever it applies (contiguous float32 /
+    float64 logits on the GPU); ``.rank`` and ``.skipped`` are then set as well.  Ties in the logits go to the lower index there, where
+    topk leaves their order open, and a target outside [0, N) is skipped and counted instead of raising.  Everywhere else: the composition."""
+
+    def __init__(self, fused=False):
+        super().__init__()
+        self.fused = bool(fused)
+        self.prec1 = self.prec5 = self.rank = self.skipped = None
+
+    def forward(self, logits, target):
+        if (self.fused and logits.is_cuda and target.is_cuda and logits.dim() == 2 and logits.is_contiguous() and logits.numel() > 0
+                and logits.dtype in (torch.float32, torch.float64) and target.dtype == torch.int64 and target.dim() == 1):
+            return _FusedClassifier.apply(logits, target, self)
+        loss = F.cross_entropy(logits, target)
+        self.rank = self.skipped = None
+        self.prec1, self.prec5 = accuracy(logits.detach(), target, (1, min(5, logits.shape[1])))
+        return loss
+
+
 def affine_residual_kernels(kz):
     """The kz^2 filters [kz^2, 1, kz, kz] (float64) whose responses, dotted with a window of the sampling grid, give the squared
     distance of that window from the nearest affine map (what losses.py:192-199 builds).  With the design matrix D of the window's

@@ -390,7 +390,8 @@ class resblock(nn.Module):
 
 class LightCNN29(nn.Module):
     """LightCNN-29 identity-feature extractor (lightcnn/light_cnn.py:82-129): forward(gray[B,1,128,128])
-    -> (logits, fc[B,256], pool[B,128,8,8])."""
+    -> (logits, fc[B,256], pool[B,128,8,8]).  ``dropout_mask`` [B,256], already scaled, replaces F.dropout's draw in train mode
+    (fixtures and tests: a run that must be repeatable)."""
 
     def __init__(self, num_classes=79077):
         super().__init__()
@@ -404,13 +405,17 @@ class LightCNN29(nn.Module):
         self.fc = mfm(8 * 8 * 128, 256, type=0)
         self.fc2 = nn.Linear(256, num_classes)
 
-    def forward(self, x):
+    def forward(self, x, dropout_mask=None):
         x = self.pool1(self.conv1(x))
         x = self.pool2(self.group1(self.block1(x)))
         x = self.pool3(self.group2(self.block2(x)))
         x = self.group3(self.block3(x))
         p = self.pool4(self.group4(self.block4(x)))
-        fc = F.dropout(self.fc(p.flatten(1)), training=self.training)
+        fc = self.fc(p.flatten(1))
+        if dropout_mask is not None and self.training:
+            fc = fc * dropout_mask
+        else:
+            fc = F.dropout(fc, training=self.training)
         return self.fc2(fc), fc, p
 
 

@@ -607,6 +607,55 @@ def landmark_loss(flows, lm_S, lm_F, gate, divisors, weights, want_grad, out_gra
     return out, grads, skipped
 
 
+# ---------------------------------------------------------------- classifier loss (csrc/softmax_xent.hip)
+def softmax_xent_chunk():
+    """Elements of a row that one block reduces (the shapes around it are where the kernel takes another path)."""
+    return _lib.load().ffwm_softmax_xent_chunk()
+
+
+def softmax_xent(logits, target, want_grad=True, out_grad=None):
+    """-> (out[3], row_loss[B], rank[B] int32, grad or None, skipped): nn.CrossEntropyLoss (mean) over logits [B, N] with int64
+    targets [B], and the reference's accuracy(output, target, (1, 5)), in one call.  out = (mean loss, prec@1, prec@5 in percent);
+    row_loss[b] = logsumexp(x_b) - x_b[t_b]; rank[b] = the elements above the target's logit plus the equal ones in front of it;
+    grad = d(mean loss)/d(logits), every element written (out_grad, where given, is the destination: contiguous, of the logits'
+    shape, dtype and device).  skipped: a device int32 scalar, the rows with a target outside [0, N): loss 0, gradient row 0, rank N."""
+    name = "softmax_xent"
+    if not (torch.is_tensor(logits) and torch.is_tensor(target)) or logits.dim() != 2 or target.dim() != 1 \
+            or target.shape[0] != logits.shape[0]:
+        raise ValueError("%s: logits [B, N] and target [B] expected" % name)
+    for t in (logits, target):
+        if not t.is_cuda:
+            raise NotImplementedError("%s: ffwm_amd ops run on the GPU only (got a %s tensor)" % (name, t.device))
+    if target.device != logits.device:
+        raise ValueError("%s: target must live on the logits' device" % name)
+    if target.dtype != torch.int64:
+        raise TypeError("%s: target must be an int64 tensor" % name)
+    if not logits.is_contiguous():
+        raise ValueError("%s: logits must be contiguous" % name)
+    B, N = logits.shape
+    if B == 0 or N == 0:
+        raise ValueError("%s: B and N must be positive (the mean of nothing)" % name)
+    code = _dtype_code(logits)
+    target = target.contiguous()
+    grad = None
+    if want_grad:
+        grad = out_grad if out_grad is not None else torch.empty_like(logits)
+        if grad.shape != logits.shape or grad.dtype != logits.dtype or grad.device != logits.device or not grad.is_contiguous():
+            raise ValueError("%s: the gradient destination must be a contiguous tensor of the logits' shape, dtype and device" % name)
+    lib = _lib.load()
+    nbytes = lib.ffwm_softmax_xent_workspace_bytes(B, N, code)
+    _lib.check(min(nbytes, 0), "ffwm_softmax_xent_workspace_bytes")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=logits.device)
+    out = logits.new_empty(3)
+    row_loss = logits.new_empty(B)
+    rank = torch.empty(B, dtype=torch.int32, device=logits.device)
+    skipped = torch.empty((), dtype=torch.int32, device=logits.device)
+    with _on_device(logits) as stream:
+        _lib.check(lib.ffwm_softmax_xent(_ptr(logits), _ptr(target), _ptr(out), _ptr(row_loss), _ptr(rank), _ptr(grad), _ptr(skipped),
+                                         _ptr(ws), B, N, code, stream), "ffwm_softmax_xent")
+    return out, row_loss, rank, grad, skipped
+
+
 # ---------------------------------------------------------------- conv weight gradient (MFMA)
 def conv3x3_wgrad_supported(input, grad_output):
     """Shapes the MFMA weight-gradient kernel takes: float32 NCHW, W a multiple of 64, below 4 GiB."""

@@ -5,6 +5,9 @@ The gradients already live in the data-parallel reducer's flat array (dp.Buckete
 moves the parameters of one optimizer into a flat array laid out the same way (``param.data`` becomes a view of
 it -- the Parameter objects, their names and state dicts are untouched) and keeps both moment estimates flat.
 Like the reference's checkpoints (models/base_model.py:save_networks), optimizer state is not saved.
+
+FlatSGD: the same for torch.optim.SGD with momentum and one (learning rate, weight decay) per parameter group
+(lightcnn/finetune.py:74-90), csrc/sgd.hip.
 """
 import torch
 
@@ -92,6 +95,116 @@ class FlatAdam(object):
                                                       self.exp_avg_sq.data_ptr(), self.n, self.lr, self.betas[0], self.betas[1],
                                                       self.eps, self.steps, _lib.F32, torch.cuda.current_stream(dev).cuda_stream),
                            "ffwm_adam_step")
+        finally:
+            if cur != dev:
+                torch.cuda.set_device(cur)
+
+    def zero_grad(self, set_to_none=False):      # the reducer owns the gradients
+        self.reducer.flat[self.lo:self.hi].zero_()
+
+
+class FlatSGD(object):
+    """torch.optim.SGD (momentum, dampening 0, no Nesterov) with per-group learning rate and weight decay as ONE streaming kernel per
+    step over flat arrays (csrc/sgd.hip) -- FlatAdam's sibling for lightcnn/finetune.py:74-90, which builds one group per tensor.
+
+    ``param_groups``: torch's form, dicts with 'params' (a tensor or a list), 'lr' and 'weight_decay' (missing keys take the
+    ``lr`` / ``weight_decay`` defaults).  The parameters become views of one flat array laid out like the reducer's gradient array;
+    every parameter is a segment of it (its padding included), and the segments whose (lr, weight_decay) are equal share one of at
+    most 16 device groups.  ``self.param_groups`` keeps one entry per group the caller passed: a scheduler writes
+    ``param_groups[i]['lr']``, and ``sync_lr()`` (called by step(), or from the host before a replay) puts the changed values into
+    the device tables, where a captured step reads them.
+
+    ``capturable`` exists for interface parity with FlatAdam (the trainers pass it and look it up in ``param_groups[0]``): the kernel
+    always reads its rates from the device tables and keeps no step counter, so every FlatSGD step can sit inside a captured hipGraph.
+    Likewise the 'momentum' entry of a group is torch's key for readers of ``param_groups``; the step uses ``self.momentum``."""
+
+    MAX_GROUPS = 16
+    MAX_SEGMENTS = 1024
+
+    def __init__(self, param_groups, reducer, momentum=0.9, capturable=False, lr=1e-3, weight_decay=0.0):
+        groups = []
+        for g in param_groups:
+            ps = [g["params"]] if torch.is_tensor(g["params"]) else list(g["params"])
+            ps = [p for p in ps if p.requires_grad]
+            if ps:
+                groups.append({"params": ps, "lr": float(g.get("lr", lr)), "weight_decay": float(g.get("weight_decay", weight_decay)),
+                               "momentum": float(momentum), "capturable": bool(capturable)})
+        params = [p for g in groups for p in g["params"]]
+        if reducer.flat is None or not params:
+            raise ValueError("FlatSGD needs a reducer with one flat gradient array and at least one parameter")
+        if len(set(map(id, params))) != len(params):
+            raise ValueError("FlatSGD: a parameter appears in more than one group")
+        spans = sorted(reducer.offset[p] for p in params)
+        self.lo, self.hi = spans[0][0], spans[-1][1]
+        inside = [p for p, (a, b) in reducer.offset.items() if a >= self.lo and b <= self.hi]
+        if len(inside) != len(params) or set(map(id, inside)) != set(map(id, params)):
+            raise ValueError("FlatSGD: the parameters are not a contiguous range of the reducer's flat layout")
+        if self.lo % 4:
+            raise ValueError("FlatSGD: range start is not 16-byte aligned")
+        if len(params) > self.MAX_SEGMENTS:
+            raise ValueError("FlatSGD: at most %d parameter tensors (csrc/sgd.hip stages the segment table in LDS)" % self.MAX_SEGMENTS)
+        self.reducer = reducer
+        self.momentum = float(momentum)
+        n = self.hi - self.lo
+        dev, dt = reducer.flat.device, reducer.flat.dtype
+        if dt != torch.float32 or dev.type != "cuda":
+            raise NotImplementedError("FlatSGD runs on float32 CUDA parameters only (csrc/sgd.hip)")
+        self.params = torch.zeros(n, device=dev, dtype=dt)
+        self.momentum_buf = torch.zeros(n, device=dev, dtype=dt)
+        with torch.no_grad():
+            for p in params:
+                a, b = reducer.offset[p]
+                view = self.params[a - self.lo:b - self.lo].view_as(p)
+                view.copy_(p.data)
+                p.data = view
+                p._ffwm_flat_adam = True       # updated by a raw-pointer kernel: the version counter does not see it (conv.frozen_cache)
+        self.n = n
+        self.steps = 0
+        self.capturable = bool(capturable)
+        self.param_groups = groups
+        # a segment = one parameter and the padding behind it: it ends where the next parameter begins
+        owner = {id(p): i for i, g in enumerate(groups) for p in g["params"]}
+        order = sorted(params, key=lambda p: reducer.offset[p][0])
+        self._seg_owner = [owner[id(p)] for p in order]
+        ends = [reducer.offset[p][0] - self.lo for p in order[1:]] + [n]
+        self.seg_end = torch.tensor(ends, dtype=torch.int64, device=dev)
+        self.seg_group = torch.zeros(len(order), dtype=torch.int32, device=dev)
+        self.group_lr = torch.zeros(self.MAX_GROUPS, dtype=torch.float64, device=dev)
+        self.group_wd = torch.zeros(self.MAX_GROUPS, dtype=torch.float64, device=dev)
+        self._on_device = None
+        self.sync_lr()
+
+    def sync_lr(self):
+        """Put the (lr, weight_decay) of every caller group into the device tables when any of them changed since the last call.
+        Outside a capture only: a replay runs no Python, so call it (or step()) from the host after the scheduler ran.
+        -> the learning rates, one per caller group."""
+        pairs = [(float(g["lr"]), float(g["weight_decay"])) for g in self.param_groups]
+        if pairs != self._on_device and not torch.cuda.is_current_stream_capturing():
+            table = sorted(set(pairs))
+            if len(table) > self.MAX_GROUPS:
+                raise ValueError("FlatSGD: %d different (lr, weight_decay) settings, csrc/sgd.hip takes %d" % (len(table), self.MAX_GROUPS))
+            index = {pair: i for i, pair in enumerate(table)}
+            pad = self.MAX_GROUPS - len(table)
+            # written in place: a captured step holds these addresses
+            self.seg_group.copy_(torch.tensor([index[pairs[o]] for o in self._seg_owner], dtype=torch.int32))
+            self.group_lr.copy_(torch.tensor([t[0] for t in table] + [0.0] * pad, dtype=torch.float64))
+            self.group_wd.copy_(torch.tensor([t[1] for t in table] + [0.0] * pad, dtype=torch.float64))
+            self._on_device = pairs
+        return [p[0] for p in pairs]
+
+    def step(self):
+        self.sync_lr()
+        self.steps += 1
+        g = self.reducer.flat[self.lo:self.hi]
+        dev = self.params.device.index
+        cur = torch.cuda.current_device()
+        if cur != dev:
+            torch.cuda.set_device(dev)
+        try:
+            _lib.check(_lib.load().ffwm_sgd_step(self.params.data_ptr(), g.data_ptr(), self.momentum_buf.data_ptr(), self.n,
+                                                 self.seg_end.data_ptr(), self.seg_group.data_ptr(), self.seg_end.numel(),
+                                                 self.group_lr.data_ptr(), self.group_wd.data_ptr(), self.MAX_GROUPS, self.momentum,
+                                                 _lib.F32, torch.cuda.current_stream(dev).cuda_stream), "ffwm_sgd_step")
         finally:
             if cur != dev:
                 torch.cuda.set_device(cur)

@@ -1095,6 +1095,19 @@ class FFWMTrainer(object):
             if path is not None:
                 _load_state_file(getattr(self, name), path, self.device)
 
+    def load_lightcnn(self, path):
+        """--lightcnn of train_ffwm.py (models/ffwm_model.py:41,212-215): `path` is a plain LightCNN-29 state dict, e.g. the
+        'lightCNN_10_checkpoint.pth' that fine-tuning wrote (LightCNNTrainer.save_checkpoint).  Loaded in place into the frozen
+        identity network, which stays in eval mode; the transformed weights of its small-plane layers are made again."""
+        self._no_eager_while_captured("load_lightcnn")
+        _load_state_file(self.lightCNN, path, self.device)
+        self.lightCNN.eval()
+        for p in self.lightCNN.parameters():
+            p.requires_grad = False
+        if self.device.type == "cuda":
+            from .conv import wg_prepare
+            wg_prepare(self.lightCNN)
+
     def _no_eager_while_captured(self, what):
         """Vendor convolutions issued eagerly between replays of a captured step made the replays read freed memory (measured in
         round 3; not root-caused: MIOpen's workspaces of the eager calls and the graph's private pool meet
@@ -1309,3 +1322,218 @@ class FlowNetTrainer(object):
         import os
         for name in self.MODEL_NAMES:
             _load_state_file(getattr(self, name), os.path.join(load_dir, "%s_net_%s.pth" % (epoch, name)), self.device)
+
+
+class LightCNNTrainer(object):
+    """Fine-tuning of the identity network, the last trainer of the reference (lightcnn/finetune.py): it writes the
+    'lightCNN_10_checkpoint.pth' that train_ffwm.py --lightcnn (FFWMTrainer.load_lightcnn) and test_ffwm.py --lightcnn read.
+        output, _, _ = LightCNN_29Layers(num_classes)(img)                 train mode: dropout in front of fc2
+        loss = CrossEntropyLoss(output, target); prec@1, prec@5 = accuracy(output, target, (1, 5))
+        SGD(momentum 0.9), one group per tensor (finetune.py:74-86):
+            bias 2 x lr without decay, fc2.bias 20 x lr without decay, fc2.weight 10 x lr, every other weight 1 x lr, both with decay
+    On the GPU the loss, its gradient and both precisions are one call (csrc/softmax_xent.hip, ``fused_loss``) and the optimizer is
+    one streaming kernel over flat arrays (csrc/sgd.hip, ``flat_sgd``); None takes the measured default of each
+    (profiles/lightcnn_finetune.txt).  The convolutions stay on the vendor library, their bias + max-feature-map on csrc/mfm.hip."""
+
+    LR_SCALE, LR_STEP = 0.457305051927326, 25          # finetune.py:283-291
+    FUSED_LOSS_DEFAULT = True
+    FLAT_SGD_DEFAULT = True
+
+    def __init__(self, device, num_classes=79077, lr=1e-4, momentum=0.9, weight_decay=1e-4, seed=0, fused_loss=None, flat_sgd=None,
+                 capturable=False, bucket_bytes=64 << 20):
+        from .losses import ClassifierLoss
+        self.device = torch.device(device)
+        torch.manual_seed(seed)
+        cuda = self.device.type == "cuda"
+        if cuda:
+            from . import miopen_tuning
+            miopen_tuning.install()
+        self.num_classes = int(num_classes)
+        self.lr, self.momentum, self.weight_decay = float(lr), float(momentum), float(weight_decay)
+        self.net = nets.LightCNN29(self.num_classes).to(self.device).train()
+        self.fused_loss = (cuda and self.FUSED_LOSS_DEFAULT) if fused_loss is None else (bool(fused_loss) and cuda)
+        self.flat_sgd = (cuda and self.FLAT_SGD_DEFAULT) if flat_sgd is None else (bool(flat_sgd) and cuda)
+        self.capturable = bool(capturable) and cuda
+        self.bucket_bytes = bucket_bytes
+        self.criterion = ClassifierLoss(fused=self.fused_loss)
+        self._build_optimizer()
+        self.losses = {}
+        self.logits = None
+        self.keep_logits_grad = False          # tests: d(loss)/d(logits) of the last step in .grad_logits
+        self.grad_logits = None
+        self._graphs = None
+        self._static = None
+
+    def parameter_groups(self):
+        """finetune.py:74-86, in named_parameters() order: one group per tensor."""
+        groups = []
+        for name, value in self.net.named_parameters():
+            if "bias" in name:
+                groups.append({"params": value, "lr": (20 if "fc2" in name else 2) * self.lr, "weight_decay": 0})
+            else:
+                groups.append({"params": value, "lr": (10 if "fc2" in name else 1) * self.lr, "weight_decay": self.weight_decay})
+        return groups
+
+    def _build_optimizer(self):
+        params = list(self.net.parameters())
+        self.reducer = BucketedGradReducer(params, bucket_bytes=self.bucket_bytes, gather=True)
+        if self.flat_sgd:
+            from .optim import FlatSGD
+            self.optimizer = FlatSGD(self.parameter_groups(), self.reducer, momentum=self.momentum, capturable=self.capturable)
+        else:
+            self.optimizer = torch.optim.SGD(self.parameter_groups(), self.lr, momentum=self.momentum, weight_decay=self.weight_decay)
+
+    def cast(self, dtype):
+        """The network in another floating type (tests: float64 on the CPU), with a fresh reducer and optimizer."""
+        if self.flat_sgd and dtype != torch.float32:
+            raise NotImplementedError("LightCNNTrainer.cast: FlatSGD runs on float32 parameters only")
+        self.net.to(dtype)
+        self._build_optimizer()
+        return self
+
+    @staticmethod
+    def targets_from_names(names):
+        """finetune.py:146-148: the class of a training image is the number its file name begins with, counted from 1."""
+        import os
+        return torch.tensor([int(os.path.basename(x)[:3]) - 1 for x in names], dtype=torch.int64)
+
+    def _seg_backward(self, b):
+        logits, _, _ = self.net(b["img"], dropout_mask=b.get("dropout_mask"))
+        if self.keep_logits_grad:
+            logits.retain_grad()
+        loss = self.criterion(logits, b["target"])
+        self.reducer.zero_grad()
+        loss.backward()
+        self.logits = logits.detach()
+        self.grad_logits = logits.grad if self.keep_logits_grad else None
+        self.losses = {"loss": loss.detach(), "prec1": self.criterion.prec1, "prec5": self.criterion.prec5}
+
+    def _batch(self, batch, dropout_mask):
+        b = {"img": batch["img"], "target": batch["target"]}
+        if dropout_mask is None:
+            dropout_mask = batch.get("dropout_mask")
+        if dropout_mask is not None:
+            b["dropout_mask"] = dropout_mask
+        return b
+
+    def step(self, batch, dropout_mask=None):
+        """train()'s loop body (finetune.py:145-162).  batch = {"img": [B,1,128,128], "target": int64 [B]} -> {"loss", "prec1",
+        "prec5"} as scalars on the device; `dropout_mask` [B,256], already scaled, replaces F.dropout's draw."""
+        b = self._batch(batch, dropout_mask)
+        if self._graphs is not None:
+            if set(b) != set(self._static):
+                raise ValueError("LightCNNTrainer.step: the captured step was built %s a dropout mask"
+                                 % ("with" if "dropout_mask" in self._static else "without"))
+            for k, v in self._static.items():
+                if b[k] is not v:
+                    v.copy_(b[k], non_blocking=True)
+            if hasattr(self.optimizer, "sync_lr"):
+                self.optimizer.sync_lr()
+            self.reducer.begin_replay()
+            self._graphs[0].replay()
+            return self.losses
+        self._seg_backward(b)
+        self.reducer.finish()
+        self.optimizer.step()
+        return self.losses
+
+    def capture(self, batch, dropout_mask=None, warmup=3):
+        """The step as one hipGraph, as FlowNetTrainer.capture on one GPU; step() replays it from then on."""
+        assert self.device.type == "cuda" and self._graphs is None
+        if not self.capturable:
+            raise RuntimeError("capture() needs LightCNNTrainer(..., capturable=True)")
+        if not self.flat_sgd:
+            raise RuntimeError("capture() needs the flat optimizer (flat_sgd): torch.optim.SGD's learning rates are host numbers")
+        self._static = {k: v.clone() for k, v in self._batch(batch, dropout_mask).items()}
+        sb = self._static
+        self.reducer.set_overlap(False)
+        side = torch.cuda.Stream(self.device)
+        side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                self._seg_backward(sb)
+                self.reducer.finish()
+                self.optimizer.step()
+        torch.cuda.current_stream(self.device).wait_stream(side)
+        torch.cuda.synchronize(self.device)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._seg_backward(sb)
+            self.reducer.finish()
+            self.optimizer.step()
+        self._graphs = [g]
+        return self
+
+    def release_graphs(self):
+        self._graphs = None
+        self._static = None
+        self.reducer.set_overlap(True)
+        self.reducer.set_gather(True)
+
+    def loss_values(self):
+        return {k: float(v.detach()) for k, v in self.losses.items()}
+
+    def adjust_learning_rate(self, epoch):
+        """finetune.py:283-291: every group's rate times 0.457305051927326 at epochs 25, 50, ...  -> the rates, one per group.  A
+        captured step sees the new rates from its next replay (step() calls FlatSGD.sync_lr)."""
+        if epoch != 0 and epoch % self.LR_STEP == 0:
+            for group in self.optimizer.param_groups:
+                group["lr"] = group["lr"] * self.LR_SCALE
+        if hasattr(self.optimizer, "sync_lr"):
+            self.optimizer.sync_lr()
+        return [g["lr"] for g in self.optimizer.param_groups]
+
+    @torch.no_grad()
+    def validate(self, gallery_keys, gallery_images, probes, names, crop=False, batch=64):
+        """validate() (finetune.py:189-215): eval mode, the features of the gallery (one image [1 | 3 dims] per key; with `crop` the
+        reference's slice [:, :, 28:-2, 15:-15] resized to 128 x 128 bilinearly -- not the grid crop of --crop), every probe [P,1,128,128]
+        ranked by cosine similarity against them.  -> RankMeter.  Train mode is restored afterwards."""
+        from .identity_eval import RankMeter, torch_cosine_topk
+        if self._graphs is not None:
+            raise RuntimeError("validate: the step is captured in a hipGraph; eager network passes beside the live graph are not safe "
+                               "-- call release_graphs() first, capture() again afterwards")
+        meter = RankMeter()
+        was_training = self.net.training
+        self.net.eval()
+        try:
+            dtype = next(self.net.parameters()).dtype
+            feas = []
+            for key, image in zip(gallery_keys, gallery_images):
+                t = image.to(self.device, dtype)
+                if t.dim() == 3:
+                    t = t.unsqueeze(0)
+                if crop:
+                    t = F.interpolate(t[:, :, 28:-2, 15:-15], (128, 128), mode="bilinear")
+                feas.append(self.net(t)[1])
+            gallery = torch.cat(feas, 0).contiguous()
+            keys = list(gallery_keys)
+            k = min(10, gallery.shape[0])
+            for i in range(0, probes.shape[0], batch):
+                ff = self.net(probes[i:i + batch].to(self.device, dtype))[1].contiguous()
+                if self.device.type == "cuda" and ff.dtype == torch.float32:
+                    from . import ops
+                    idx = ops.cosine_topk(ff, gallery, k)[1]
+                else:
+                    idx = torch_cosine_topk(ff, gallery, k)[1]
+                meter.update(idx, list(names[i:i + batch]), keys)
+        finally:
+            self.net.train(was_training)
+        return meter
+
+    def save_checkpoint(self, save_dir, epoch):
+        """finetune.py:124-129: 'lightCNN_<epoch + 1>_checkpoint.pth' every fifth epoch and always 'lightCNN_latest_checkpoint.pth':
+        the network's state dict, CPU tensors, the reference's key names.  -> the files written."""
+        import os
+        os.makedirs(save_dir, exist_ok=True)
+        sd = {k: v.detach().cpu().clone() for k, v in self.net.state_dict().items()}
+        files = []
+        if epoch % 5 == 0:
+            files.append(os.path.join(save_dir, "lightCNN_" + str(epoch + 1) + "_checkpoint.pth"))
+        files.append(os.path.join(save_dir, "lightCNN_latest_checkpoint.pth"))
+        for f in files:
+            torch.save(sd, f)
+        return files
+
+    def load_checkpoint(self, path):
+        """finetune.py:92-94.  The parameters are written in place, so a captured step goes on with the loaded weights."""
+        _load_state_file(self.net, path, self.device)

@@ -28,6 +28,8 @@
  *   ffwm_mfm_*                      <- mfm.forward (split + max)        lightcnn/light_cnn.py
  *   ffwm_bias_relu_forward          <- conv bias add + nn.ReLU of VGG19  models/losses.py:398-519
  *   ffwm_adam_step                  <- torch.optim.Adam.step            models/ffwm_model.py:46-49,151-160
+ *   ffwm_sgd_step                   <- torch.optim.SGD.step, one group per tensor  lightcnn/finetune.py:74-90
+ *   ffwm_softmax_xent               <- nn.CrossEntropyLoss + accuracy(output, target, (1, 5))  lightcnn/finetune.py:109,152-159
  *   ffwm_l1_multi                   <- the w * F.l1_loss(x * m, y * m) terms of backward_G   models/ffwm_model.py:107-139
  *   ffwm_conv2d_wgrad[_tiled]       <- convolution_backward grad_weight of the stride-2 / transposed / small-plane convs
  *
@@ -619,6 +621,35 @@ int ffwm_adam_step(void* params, const void* grads, void* exp_avg, void* exp_avg
  * "no override" (ABI 4; ABI 3 took 0 for "none", so a schedule that reached 0.0 could not freeze the weights).  Two launches. */
 int ffwm_adam_step_device(void* params, const void* grads, void* exp_avg, void* exp_avg_sq, int64_t n, double lr, double beta1,
                           double beta2, double eps, void* state, int dtype, void* stream);
+
+/* One SGD-momentum step (torch.optim.SGD with dampening 0 and no Nesterov, as lightcnn/finetune.py:88-90 constructs it) over FLAT
+ * float32 arrays of n elements, 16-byte aligned: parameters, gradients and the momentum buffer (start it at zero: that is torch's
+ * first step).  Element i belongs to segment s, the first one with seg_end[s] > i (DEVICE int64, ascending, seg_end[n_seg - 1] == n,
+ * n_seg <= 1024), and takes the learning rate and the weight decay of group seg_group[s] (DEVICE int32) from group_lr / group_wd
+ * (DEVICE doubles, n_groups <= 16, rounded to float32; a group index outside the table is clamped into it):
+ *     g' = g + wd p,    buf = momentum buf + g',    p = p - lr buf      (the last line one fma: five roundings per element)
+ * Everything a schedule changes lives in device memory, so the next replay of a captured step sees it.  One launch. */
+int ffwm_sgd_step(void* params, const void* grads, void* momentum_buf, int64_t n, const int64_t* seg_end, const int32_t* seg_group,
+                  int n_seg, const double* group_lr, const double* group_wd, int n_groups, double momentum, int dtype, void* stream);
+
+/* ---- classifier loss of LightCNN fine-tuning (csrc/softmax_xent.hip; lightcnn/finetune.py:109,152-159,294-307) ---------------
+ * nn.CrossEntropyLoss (mean) over logits [B, N], its gradient, and accuracy(output, target, (1, 5)), in three launches without
+ * float atomics; float32 and float64.  target: DEVICE int64 [B].
+ *   row_loss[b] = logsumexp(x_b) - x_b[t_b]      (the row maximum subtracted; NULL: not written)
+ *   rank[b]     = #{j : x_bj > x_bt} + #{j < t : x_bj == x_bt}    (int32, NULL: not written; ties go to the lower index, a NaN ranks
+ *                 above everything and equal to another NaN: ffwm_cosine_topk's rule)
+ *   grad_logits[b, j] = (softmax(x_b)[j] - [j == t_b]) / B        (NULL: not written; else OVERWRITTEN completely)
+ *   out[0] = mean of row_loss,  out[1] / out[2] = 100 #{b : rank[b] < 1 / 5} / B
+ * A NaN logit makes its row's loss and gradient NaN, and out[0]; a -inf logit adds exp = 0 and gets a gradient of exactly 0; +inf
+ * is not covered.  A row whose target lies outside [0, N) is never dereferenced with it: row loss 0, gradient row 0, rank N, and it
+ * counts in *skipped (a device int32, overwritten); the mean still divides by B.
+ * A row is reduced in chunks of ffwm_softmax_xent_chunk() elements, the chunks' sums meet in double in an order fixed by the
+ * shapes: two calls agree bit for bit.  workspace: ffwm_softmax_xent_workspace_bytes bytes, 8-byte aligned, contents irrelevant on
+ * entry and exit (a negative ffwm_status for sizes the entry point refuses).  N up to 2^24, B up to 65535; beyond: FFWM_ERR_SIZE. */
+int ffwm_softmax_xent_chunk(void);
+int64_t ffwm_softmax_xent_workspace_bytes(int64_t B, int64_t N, int dtype);
+int ffwm_softmax_xent(const void* logits, const int64_t* target, void* out, void* row_loss, int* rank, void* grad_logits,
+                      int* skipped, void* workspace, int64_t B, int64_t N, int dtype, void* stream);
 
 /* ---- netG eval forward (models/base_networks.py:274-347): the layers around the dense convolutions once BatchNorm is folded
  * into the conv weights (ffwm_amd/ffwm_eval.py, csrc/netg_eval.hip).  float32, forward only.

@@ -1,0 +1,241 @@
+"""What the fused classifier loss (csrc/softmax_xent.hip) and the flat SGD step (csrc/sgd.hip) buy in LightCNN fine-tuning, measured
+on an MI355X at the reference's shapes (batch 10, 79 077 classes, lightcnn/finetune.py):
+
+    python tools/finetune_bench.py [--pairs 5] [--out profiles/lightcnn_finetune.txt]
+
+(a) loss + prec@1 / prec@5, forward + backward, on logits [10, 79077]: A = the ATen composition (F.cross_entropy + accuracy()),
+    B = ClassifierLoss(fused=True), one call of ffwm_softmax_xent.
+(b) the optimizer step over LightCNN-29's 62 parameter groups: A = torch.optim.SGD, B = optim.FlatSGD, with GB/s over the model of
+    20 bytes per parameter.
+(c) the captured LightCNNTrainer step at batch 10 with both switches off (A: the composition's loss, torch.optim.SGD inside the
+    graph) and both on (B).  One graph is alive at a time: every window captures its trainer's step afresh and drops the graph again,
+    because the eager warm-up of a capture issues vendor convolutions, which must not run beside a live graph that holds them.
+Every leg is device time inside a captured graph (launches this small time the host's dispatch when they are issued eagerly), replayed
+and timed with device events; A and B alternate for --pairs pairs and are reported as median and min-max, with the profiler's kernel
+event count of one eager run of each.  "B below A by more than the larger min-max spread" is the rule the trainer's defaults follow.
+Every part is a child process under its own time limit; the parent never opens the GPU, stops at the first part that fails; --out is
+written only when all three parts ended well (a failed run writes what it has to <out>.failed).  GPU only: without a device the tool fails.
+"""
+import argparse
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+DEV = "cuda:0"
+LIMITS = {"a": 240, "b": 300, "c": 420}          # seconds per child
+B, N = 10, 79077
+
+
+def captured(stage, calls):
+    """`calls` runs of stage() in one graph -> a function that replays it and returns device ms per run."""
+    import torch
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(3):
+            stage()
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(calls):
+            stage()
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def replay(reps=5):
+        times = []
+        for _ in range(reps + 1):
+            start.record()
+            g.replay()
+            stop.record()
+            stop.synchronize()
+            times.append(start.elapsed_time(stop) / calls)
+        return statistics.median(times[1:])
+    return replay
+
+
+def kernel_count(fn):
+    """Device kernels of one fn() as torch's profiler sees them (None when it is not available)."""
+    import torch
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        return sum(e.count for e in prof.key_averages() if getattr(e, "device_time_total", 0) > 0 or getattr(e, "cuda_time_total", 0) > 0)
+    except Exception:          # noqa: BLE001  (a count is a remark in the report, never a reason to lose the timings)
+        return None
+
+
+def line(name, vals, unit, scale=1.0):
+    return "%s  median %.3f %s  min %.3f  max %.3f  runs [%s]" % (name, scale * statistics.median(vals), unit, scale * min(vals),
+                                                                  scale * max(vals), ", ".join("%.3f" % (scale * v) for v in vals))
+
+
+def verdict(tag, ms, unit, scale):
+    margin = statistics.median(ms["A"]) - statistics.median(ms["B"])
+    worst = max(max(ms["A"]) - min(ms["A"]), max(ms["B"]) - min(ms["B"]))
+    print("%s  A - B = %.3f %s against the larger min-max spread %.3f %s: B is %s; A / B = %.2f" % (
+        tag, scale * margin, unit, scale * worst, unit, "below A by more than the spread" if margin > worst else
+        ("NOT below A by more than the spread" if margin >= -worst else "SLOWER than A beyond the spread"),
+        statistics.median(ms["A"]) / statistics.median(ms["B"])))
+
+
+def alternate(ra, rb, pairs):
+    ms = {"A": [], "B": []}
+    for _ in range(pairs):
+        ms["A"].append(ra())
+        ms["B"].append(rb())
+    return ms
+
+
+def part_a(args):
+    import torch
+    from ffwm_amd import losses
+    gen = torch.Generator().manual_seed(2)
+    logits = torch.randn(B, N, generator=gen).to(DEV).requires_grad_(True)
+    target = torch.randint(0, N, (B,), generator=gen).to(DEV)
+    modules = {"A": losses.ClassifierLoss(), "B": losses.ClassifierLoss(fused=True)}
+    keep = {}
+
+    def stage(which):
+        def run():
+            crit = modules[which]
+            loss = crit(logits, target)
+            keep["loss"], keep["g"], keep["prec"] = loss.detach(), torch.autograd.grad(loss, logits)[0], (crit.prec1, crit.prec5)
+        return run
+
+    stage("A")()
+    la, ga, pa = keep["loss"].clone(), keep["g"].clone(), [float(v) for v in keep["prec"]]
+    stage("B")()
+    print("# (a) loss + prec@1 / prec@5, forward + backward, logits [%d, %d], float32, device %s" % (B, N, torch.cuda.get_device_name(0)))
+    print("#     A = F.cross_entropy + accuracy(), B = ClassifierLoss(fused=True); %d evaluations per captured graph, median of 5 replays "
+          "per run, %d alternating pairs" % (args.calls, args.pairs))
+    print("a  loss A %.7f  B %.7f;  prec A %s  B %s;  max |gradient A - B| %.3e (max |gradient| %.3e)" % (
+        float(la), float(keep["loss"]), pa, [float(v) for v in keep["prec"]], (ga - keep["g"]).abs().max().item(), ga.abs().max().item()))
+    ms = alternate(captured(stage("A"), args.calls), captured(stage("B"), args.calls), args.pairs)
+    print(line("a  A (composition)", ms["A"], "us", 1e3))
+    print(line("a  B (fused)      ", ms["B"], "us", 1e3))
+    verdict("a", ms, "us", 1e3)
+    na, nb = kernel_count(stage("A")), kernel_count(stage("B"))
+    print("a  device kernel events of one eager evaluation (profiler): A %s, B %s" % (
+        na if na is not None else "not measured", nb if nb is not None else "not measured"), flush=True)
+
+
+def part_b(args):
+    import torch
+    from ffwm_amd import trainer
+    ta = trainer.LightCNNTrainer(DEV, seed=0, fused_loss=False, flat_sgd=False)
+    tb = trainer.LightCNNTrainer(DEV, seed=0, fused_loss=False, flat_sgd=True, capturable=True)
+    gen = torch.Generator().manual_seed(3)
+    for t in (ta, tb):
+        t.reducer.set_gather(False)          # the gradients are the reducer's views: filled once, both optimizers read them
+    for p, q in zip(ta.net.parameters(), tb.net.parameters()):
+        g = (torch.randn(p.shape, generator=gen) * 1e-3).to(DEV)
+        p.grad.copy_(g)
+        q.grad.copy_(g)
+    n = sum(p.numel() for p in ta.net.parameters())
+    print("# (b) the optimizer step over LightCNN-29 (%d parameters in %d groups), float32" % (n, len(ta.optimizer.param_groups)))
+    print("#     A = torch.optim.SGD (momentum 0.9, one group per tensor), B = optim.FlatSGD (one launch of ffwm_sgd_step); %d steps per "
+          "captured graph, median of 5 replays per run, %d alternating pairs" % (args.calls, args.pairs))
+    ms = alternate(captured(ta.optimizer.step, args.calls), captured(tb.optimizer.step, args.calls), args.pairs)
+    print(line("b  A (torch.optim.SGD)", ms["A"], "us", 1e3))
+    print(line("b  B (FlatSGD)        ", ms["B"], "us", 1e3))
+    for k in ("A", "B"):
+        print("b  %s  %.0f GB/s over 20 bytes per parameter" % (k, 20.0 * n / (statistics.median(ms[k]) * 1e-3) / 1e9))
+    verdict("b", ms, "us", 1e3)
+    na, nb = kernel_count(ta.optimizer.step), kernel_count(tb.optimizer.step)
+    print("b  device kernel events of one eager step (profiler): A %s, B %s" % (
+        na if na is not None else "not measured", nb if nb is not None else "not measured"), flush=True)
+
+
+def part_c(args):
+    import torch
+    from ffwm_amd import trainer
+    gen = torch.Generator().manual_seed(4)
+    batch = {"img": torch.rand(B, 1, 128, 128, generator=gen).to(DEV), "target": torch.randint(0, N, (B,), generator=gen).to(DEV)}
+    ts = {"A": trainer.LightCNNTrainer(DEV, seed=0, fused_loss=False, flat_sgd=False),
+          "B": trainer.LightCNNTrainer(DEV, seed=0, fused_loss=True, flat_sgd=True, capturable=True)}
+    counts = {k: kernel_count(lambda t=t: t.step(batch)) for k, t in ts.items()}
+
+    def one(t):
+        def run():
+            t._seg_backward(batch)
+            t.reducer.finish()
+            t.optimizer.step()
+        return run
+    for t in ts.values():
+        t.reducer.set_overlap(False)
+    print("# (c) the LightCNNTrainer step at batch %d, %d classes, as one captured graph: A = fused_loss and flat_sgd off, B = both on; "
+          "%d steps per window, %d alternating pairs; ONE graph alive at a time (each window captures its trainer's step afresh and "
+          "drops the graph before the other trainer issues anything)" % (B, N, args.steps, args.pairs))
+
+    def window(t):
+        # The network's convolutions are the vendor library's: none of them may be issued eagerly beside a live graph that holds
+        # them ("one process, one captured trainer"), and the warm-up of a capture is eager.
+        replay = captured(one(t), args.steps)
+        ms = replay()
+        del replay
+        torch.cuda.synchronize()
+        return ms
+    ms = alternate(lambda: window(ts["A"]), lambda: window(ts["B"]), args.pairs)
+    print(line("c  A (both off)", ms["A"], "ms"))
+    print(line("c  B (both on) ", ms["B"], "ms"))
+    verdict("c", ms, "ms", 1.0)
+    print("c  device kernel events of one eager step (profiler): A %s, B %s" % tuple(
+        counts[k] if counts[k] is not None else "not measured" for k in ("A", "B")))
+    print("c  last loss: A %.6g, B %.6g" % (float(ts["A"].losses["loss"]), float(ts["B"].losses["loss"])), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pairs", type=int, default=5)
+    ap.add_argument("--calls", type=int, default=20, help="evaluations per captured graph, parts (a) and (b)")
+    ap.add_argument("--steps", type=int, default=5, help="train steps per captured graph, part (c)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lightcnn_finetune.txt"))
+    ap.add_argument("--part", choices=("a", "b", "c"), help="run one GPU part in this process (what the parent starts)")
+    args = ap.parse_args()
+    if args.pairs < 5:
+        sys.exit("finetune_bench: at least five pairs")
+    if args.part:
+        import torch
+        if not torch.cuda.is_available():
+            sys.exit("finetune_bench: needs an MI355X; a CPU run measures nothing")
+        return {"a": part_a, "b": part_b, "c": part_c}[args.part](args)
+
+    lines = []
+    common = [sys.executable, os.path.abspath(__file__), "--pairs", str(args.pairs), "--calls", str(args.calls), "--steps", str(args.steps)]
+    status = 0
+    for part in ("a", "b", "c"):
+        try:
+            r = subprocess.run(common + ["--part", part], capture_output=True, text=True, timeout=LIMITS[part], cwd=ROOT)
+            text, status = r.stdout, r.returncode
+            if status != 0:
+                last = [ln for ln in r.stderr.strip().splitlines() if ln.strip()][-1:]
+                text += "finetune_bench: part %s ended with status %d: %s\n" % (part, status, last[0] if last else "")
+                sys.stderr.write(r.stderr[-4000:])
+        except subprocess.TimeoutExpired as e:
+            text = (e.stdout.decode() if isinstance(e.stdout, bytes) else e.stdout or "") \
+                + "finetune_bench: part %s passed its limit of %d s\n" % (part, LIMITS[part])
+            status = 124
+        print(text, end="", flush=True)
+        lines.append(text)
+        if status != 0:
+            break              # nothing more is started on the GPU after a part that failed
+    # the report replaces --out only when all three parts ended well; a run that failed (no GPU, a part past its limit) leaves what is
+    # there alone and writes what it has beside it
+    out = args.out if status == 0 else args.out + ".failed"
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        f.write("".join(lines))
+    if status != 0:
+        sys.stderr.write("finetune_bench: status %d, %s is unchanged; the partial report is %s\n" % (status, args.out, out))
+    sys.exit(status)
+
+
+if __name__ == "__main__":
+    main()
