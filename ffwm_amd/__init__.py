@@ -20,6 +20,10 @@ csyxwei/FFWM: hand-written HIP kernels behind the reference's own operator API.
     ffwm_amd.FaceIdentifier      the rest of that loop: Frontalizer -> (centre-face crop) -> LightCNN-29 feature -> cosine top-k
                                  against a gallery, one captured hipGraph (ffwm_amd.identity_eval; FoldedLightCNN is the feature
                                  network alone, IdentityResult what a call returns, RankMeter the by-pose rank-1 meter)
+    ffwm_amd.FaceStore           the reference's FaceDataset with --preload, kept on the device as bytes (ffwm_amd.data: from_directory /
+                                 from_arrays / .npz, pairs, s2f, the gallery, host_item / host_batch as the CPU path), and
+    ffwm_amd.FaceLoader          its DataLoader: one uploaded permutation per epoch, one gather launch per batch (csrc/face_batch.hip),
+                                 batches in the form the trainers' step() and capture() take
 """
 __version__ = "0.1.0"
 
@@ -32,4 +36,7 @@ def __getattr__(name):
     if name in ("FaceIdentifier", "FoldedLightCNN", "IdentityResult", "RankMeter"):
         from . import identity_eval
         return getattr(identity_eval, name)
+    if name in ("FaceStore", "FaceLoader", "FaceBatch"):
+        from . import data
+        return getattr(data, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

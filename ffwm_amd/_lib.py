@@ -93,6 +93,10 @@ _SIGNATURES = {
     "ffwm_identity_input": [_p, _p] + [_i64] * 4 + [_i, _i, _p],
     "ffwm_identity_input_backward": [_p, _p] + [_i64] * 4 + [_i, _i, _p],
     "ffwm_cosine_topk": [_p, _p, _p, _p] + [_i64] * 4 + [_p, _i64, _i, _p],
+    # (images, masks, pairs, pair_lm, lm, lm_flip, gate, index; img_S, img_F, mask_S, mask_F, lm_S, lm_F, gate_out, invalid;
+    #  N, H, W, P, K, KG, L, B; train, stream)
+    "ffwm_face_batch": [_p] * 16 + [_i64] * 8 + [_i, _p],
+    "ffwm_face_gallery": [_p, _p, _p] + [_i64] * 4 + [_p],
     "ffwm_prof_enable": [_i],
     "ffwm_prof_collect": [],
     "ffwm_prof_get": [_i, ctypes.c_char_p, _i, ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double),

@@ -1268,3 +1268,64 @@ def l1_multi_backward(terms, grad_out, need):
     for i, g in zip(sel, grads):
         out[i] = g
     return out
+
+
+# ---------------------------------------------------------------- device-resident face dataset
+_FACE_TABLES = (("pairs", torch.int32), ("index", torch.int32), ("masks", torch.uint8), ("pair_lm", torch.int32), ("lm", torch.int32),
+                ("lm_flip", torch.int32), ("gate", torch.float32))
+
+
+def face_batch(images, pairs, index, masks=None, pair_lm=None, lm=None, lm_flip=None, gate=None, out=None):
+    """One batch of the reference's FaceDataset from a device-resident store in ONE launch (csrc/face_batch.hip): images uint8
+    [N, H, W, 3], pairs int32 [P, 2], index int32 [B] ON THE DEVICE -> {"img_S", "img_F": float32 [B, 3, H, W], "invalid": int32 [B]}
+    (a test batch, index in [0, P)); with masks uint8 [N, H, W], pair_lm int32 [P, 3], lm / lm_flip int32 [K, L, 2] and gate float32
+    [KG, L] a training batch (index in [0, 2 P), >= P flipped): also "mask_S", "mask_F" [B, 1, H, W], "lm_S", "lm_F" int64 [B, L, 2],
+    "gate" [B, L, 1].  `out`: a dict of destinations of those shapes, written in place (a missing one is allocated).  No host-device
+    copy and no synchronisation: an index out of range gives zeros and invalid[b] = 1, to be read when the caller chooses."""
+    name = "face_batch"
+    train = masks is not None
+    tables = {"pairs": pairs, "index": index, "masks": masks, "pair_lm": pair_lm, "lm": lm, "lm_flip": lm_flip, "gate": gate}
+    if train and any(v is None for v in tables.values()):
+        raise ValueError("%s: a training batch needs masks, pair_lm, lm, lm_flip and gate" % name)
+    if not images.is_cuda:
+        raise NotImplementedError("%s: ffwm_amd ops run on the GPU only (got a %s tensor); FaceStore.host_batch is the CPU path"
+                                  % (name, images.device))
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3 or not images.is_contiguous():
+        raise ValueError("%s: images must be contiguous uint8 [N, H, W, 3]" % name)
+    for key, dt in _FACE_TABLES:
+        t = tables[key]
+        if train or key in ("pairs", "index"):
+            if t.dtype != dt or t.device != images.device or not t.is_contiguous():
+                raise ValueError("%s: %s must be a contiguous %s tensor on %s" % (name, key, dt, images.device))
+    N, H, W, _ = images.shape
+    if pairs.dim() != 2 or pairs.shape[1] != 2 or index.dim() != 1:
+        raise ValueError("%s: pairs must be [P, 2] and index [B]" % name)
+    P, B = pairs.shape[0], index.shape[0]
+    K = KG = L = 0
+    if train:
+        if tuple(masks.shape) != (N, H, W):
+            raise ValueError("%s: masks must be [%d, %d, %d]" % (name, N, H, W))
+        if lm.dim() != 3 or lm.shape[2] != 2 or lm_flip.shape != lm.shape or gate.dim() != 2 or gate.shape[1] != lm.shape[1] \
+                or tuple(pair_lm.shape) != (P, 3):
+            raise ValueError("%s: need lm / lm_flip [K, L, 2], gate [KG, L] and pair_lm [P, 3]" % name)
+        K, L, KG = lm.shape[0], lm.shape[1], gate.shape[0]
+    shapes = {"img_S": ((B, 3, H, W), torch.float32), "img_F": ((B, 3, H, W), torch.float32), "invalid": ((B,), torch.int32)}
+    if train:
+        shapes.update({"mask_S": ((B, 1, H, W), torch.float32), "mask_F": ((B, 1, H, W), torch.float32),
+                       "lm_S": ((B, L, 2), torch.int64), "lm_F": ((B, L, 2), torch.int64), "gate": ((B, L, 1), torch.float32)})
+    res = {}
+    for key, (shape, dt) in shapes.items():
+        t = None if out is None else out.get(key)
+        if t is None:
+            t = torch.empty(shape, dtype=dt, device=images.device)
+        elif tuple(t.shape) != shape or t.dtype != dt or t.device != images.device or not t.is_contiguous():
+            raise ValueError("%s: the destination %s must be a contiguous %s tensor of shape %s on %s" % (name, key, dt, shape, images.device))
+        res[key] = t
+    if B:
+        with _on_device(images) as stream:
+            _lib.check(_lib.load().ffwm_face_batch(
+                _ptr(images), _ptr(masks), _ptr(pairs), _ptr(pair_lm), _ptr(lm), _ptr(lm_flip), _ptr(gate), _ptr(index),
+                _ptr(res["img_S"]), _ptr(res["img_F"]), _ptr(res.get("mask_S")), _ptr(res.get("mask_F")), _ptr(res.get("lm_S")),
+                _ptr(res.get("lm_F")), _ptr(res.get("gate")), _ptr(res["invalid"]), N, H, W, P, K, KG, L, B, int(train), stream),
+                "ffwm_face_batch")
+    return res

@@ -706,6 +706,30 @@ int64_t ffwm_cosine_topk_workspace_bytes(int64_t B, int64_t G, int64_t D, int64_
 int ffwm_cosine_topk(const void* probe, const void* gallery, void* values, void* indices, int64_t B, int64_t G, int64_t D, int64_t k,
                      void* workspace, int64_t workspace_bytes, int dtype, void* stream);
 
+/* ---- device-resident face dataset (csrc/face_batch.hip): the reference's data/face_dataset.py with --preload ----------------
+ * The store stays on the device as bytes; ONE launch assembles a batch from a DEVICE vector of item indices (a captured launch
+ * follows the contents of that vector).
+ *   images uint8 [N, H, W, 3] (RGB), masks uint8 [N, H, W]; pairs int32 [P, 2]: the rows of S and F of every pair;
+ *   pair_lm int32 [P, 3]: the rows of lm_S and lm_F in the landmark tables and the row of the gate table;
+ *   lm / lm_flip int32 [K, L, 2]: the landmarks as the reference delivers them (long(), clamped) without and with the flip's
+ *   x -> 127 - x, both worked out once on the host in the reference's own arithmetic; gate float32 [KG, L]; index int32 [B].
+ * train 1: index i in [0, 2 P), i >= P is the flipped copy (images and masks reversed along W, lm_flip) of pair i - P.  Written:
+ *   img_S / img_F float32 [B, 3, H, W], mask_S / mask_F float32 [B, 1, H, W] = byte / 255 (a true division), lm_S / lm_F int64
+ *   [B, L, 2], gate_out float32 [B, L, 1], invalid int32 [B].
+ * train 0 (a test batch): index in [0, P), nothing is flipped, only img_S, img_F and invalid are written; masks, pair_lm, the tables
+ *   and the other outputs are not looked at (NULL allowed).
+ * Every output element is written exactly once by a plain store (no zero-fill needed, nothing else is touched).  An index outside its
+ * range, or a table row outside its table, is never used as an address: that sample's outputs are zeros and invalid[b] = 1 (else 0).
+ * Before any launch: FFWM_ERR_ARG for a NULL pointer that the mode needs or a size <= 0, FFWM_ERR_SIZE for H or W > 8192, B > 65535,
+ * L > 2^20, N >= 2^31 or P >= 2^30. */
+int ffwm_face_batch(const void* images, const void* masks, const void* pairs, const void* pair_lm, const void* lm, const void* lm_flip,
+                    const void* gate, const void* index, void* img_S, void* img_F, void* mask_S, void* mask_F, void* lm_S, void* lm_F,
+                    void* gate_out, void* invalid, int64_t N, int64_t H, int64_t W, int64_t P, int64_t K, int64_t KG, int64_t L,
+                    int64_t B, int train, void* stream);
+/* Gallery planes: out float32 [G, 1, H, W] = ((r + g) + b) / 3 of byte / 255 of image rows[g] (int32 [G], device) -- the arithmetic
+ * of ffwm_identity_input (crop 0) on the float image.  A row outside [0, N) gives a plane of zeros.  Same argument checks. */
+int ffwm_face_gallery(const void* images, const void* rows, void* out, int64_t N, int64_t H, int64_t W, int64_t G, void* stream);
+
 /* ---- built-in per-kernel timing (HIP events on the launch stream) ---------------------------
  * ffwm_prof_enable(1) brackets every kernel launch of this library with a pair of HIP events
  * recorded on the stream the kernel is launched on.  ffwm_prof_collect() waits for the recorded
