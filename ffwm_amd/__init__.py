@@ -24,6 +24,9 @@ csyxwei/FFWM: hand-written HIP kernels behind the reference's own operator API.
                                  from_arrays / .npz, pairs, s2f, the gallery, host_item / host_batch as the CPU path), and
     ffwm_amd.FaceLoader          its DataLoader: one uploaded permutation per epoch, one gather launch per batch (csrc/face_batch.hip),
                                  batches in the form the trainers' step() and capture() take
+    ffwm_amd.IdentityStore       the reference's lightcnn ImgDataset with --preload on the device (bytes and classes), and
+    ffwm_amd.IdentityLoader      its DataLoader: PIL's bicubic RandomRotation(5), the flip, the channel mean and --crop of a whole batch
+                                 in one launch (csrc/identity_batch.hip); LightCNNTrainer.train_epoch(loader, epoch) runs an epoch
 """
 __version__ = "0.1.0"
 
@@ -36,7 +39,7 @@ def __getattr__(name):
     if name in ("FaceIdentifier", "FoldedLightCNN", "IdentityResult", "RankMeter"):
         from . import identity_eval
         return getattr(identity_eval, name)
-    if name in ("FaceStore", "FaceLoader", "FaceBatch"):
+    if name in ("FaceStore", "FaceLoader", "FaceBatch", "IdentityStore", "IdentityLoader", "IdentityBatch"):
         from . import data
         return getattr(data, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

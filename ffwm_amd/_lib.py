@@ -97,6 +97,8 @@ _SIGNATURES = {
     #  N, H, W, P, K, KG, L, B; train, stream)
     "ffwm_face_batch": [_p] * 16 + [_i64] * 8 + [_i, _p],
     "ffwm_face_gallery": [_p, _p, _p] + [_i64] * 4 + [_p],
+    # (images, targets, index, matrix, flip; img, target, invalid; N, H, W, B, out_side; augment, crop, stream)
+    "ffwm_identity_batch": [_p] * 8 + [_i64] * 5 + [_i, _i, _p],
     "ffwm_prof_enable": [_i],
     "ffwm_prof_collect": [],
     "ffwm_prof_get": [_i, ctypes.c_char_p, _i, ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double),

@@ -19,9 +19,26 @@ What the reference does and this module reproduces (face_dataset.py:37-90, 132-1
   * multipie pairs are (file, s2f(file)), other modes (file, file); a test item is img_S, img_F, input_path, unflipped;
   * the gallery is gallery_list.npy or the first *051_06.png per file[:3], each entry the channel mean of byte / 255.
 Not reproduced: the rotation of --aug (its image half is cv2.warpAffine, which cannot be checked without OpenCV: aug=True raises),
-lightcnn/dataset.py's transform, reading without --preload, sharding over ranks.  The reference walks os.listdir() order (arbitrary)
-and shuffles the files before it picks a gallery; from_directory sorts the names, so "first" means first by name.
+reading without --preload, sharding over ranks.  The reference walks os.listdir() order (arbitrary) and shuffles the files before it
+picks a gallery; from_directory sorts the names, so "first" means first by name.
+
+The input pipeline of LightCNN fine-tuning (lightcnn/dataset.py with --preload, finetune.py:98-106, 145-148) is here too:
+
+    store = IdentityStore.from_directory(dataroot, isval=False).to("cuda:0")
+    for epoch in range(epochs):
+        loss, prec1, prec5 = trainer.train_epoch(IdentityLoader(store, 64, crop=True, seed=0), epoch)
+
+IdentityStore holds the images as bytes and the class of every image (int(name[:3]) - 1); IdentityLoader draws an epoch's permutation,
+rotation angles and flips on the host, uploads them once, and assembles every batch {"img", "target"} with ONE launch of
+ops.identity_batch (csrc/identity_batch.hip) on slices of them.  What the reference does per training item and this module reproduces
+(dataset.py:19-24, 57-67): ToPILImage, RandomRotation(5, BICUBIC), RandomHorizontalFlip, ToTensor, torch.mean over the channels,
+and with --crop the slice [:, 28:-2, 15:-15] resized bilinearly to 128 x 128; a test item is byte / 255, the mean and the same crop.
+The rotation is PIL's Image.rotate: rotation_matrix and rotate_bicubic restate it in float64 (numpy; the run time needs no PIL), and
+tests/golden/pil_bicubic_rotate.npz records what PIL 12.2 gives for the same inputs -- the bytes are equal.  The reference draws its
+angles and flips from Python's global `random` inside its loader workers, so ITS sequence of draws cannot be reproduced; the
+distributions are the same.
 """
+import math
 import os
 
 import numpy as np
@@ -374,3 +391,318 @@ class FaceLoader(object):
                 self._sets[step % len(self._sets)].update(res)          # buffers the first full batch allocated are kept
             invalid = res.pop("invalid")
             yield FaceBatch(res, [names[rows_S[i % P]] for i in order[lo:hi]], hi - lo, invalid)
+
+
+# ====================================================================== LightCNN fine-tuning: lightcnn/dataset.py
+CROP_ROWS, CROP_COLS = slice(28, -2), slice(15, -15)          # dataset.py:64
+
+
+def rotation_matrix(angle, w, h):
+    """The inverse-map matrix [m0 .. m5] of Image.rotate(angle) (degrees, counter-clockwise, about the centre, expand=False) for a
+    w x h image, in Python floats with the math module, as PIL builds it."""
+    a = -math.radians(angle % 360.0)
+    m = [round(math.cos(a), 15), round(math.sin(a), 15), 0.0, round(-math.sin(a), 15), round(math.cos(a), 15), 0.0]
+    cx, cy = w / 2.0, h / 2.0
+    m[2], m[5] = m[0] * -cx + m[1] * -cy + m[2], m[3] * -cx + m[4] * -cy + m[5]
+    m[2] += cx
+    m[5] += cy
+    return m
+
+
+def _cubic(v1, v2, v3, v4, d):
+    """The a = -1 cubic through four taps at fraction d, in PIL's operation order."""
+    p1 = v2
+    p2 = -v1 + v3
+    p3 = 2 * (v1 - v2) + v3 - v4
+    p4 = -v1 + v2 - v3 + v4
+    return p1 + d * (p2 + d * (p3 + d * p4))
+
+
+def rotate_bicubic(image, matrix):
+    """Image.transform(size, AFFINE, matrix, BICUBIC) of a uint8 [H, W, 3] array, restated in float64 (numpy rounds every product
+    and sum on its own: nothing is contracted): xin = m0 (x + .5) + m1 (y + .5) + m2, yin likewise; outside [0, W) x [0, H) the
+    pixel is 0; else the cubic over 4 x 4 index-clamped taps around (xin - .5, yin - .5), rows first, clipped to [0, 255] and
+    TRUNCATED to a byte.  Image.rotate(angle, BICUBIC) is this under rotation_matrix(angle, W, H)."""
+    image = np.asarray(image)
+    H, W, _ = image.shape
+    m = [float(v) for v in matrix]
+    xs, ys = (np.arange(W, dtype=np.float64) + 0.5)[None, :], (np.arange(H, dtype=np.float64) + 0.5)[:, None]
+    with np.errstate(invalid="ignore", over="ignore"):
+        xin = m[0] * xs + m[1] * ys + m[2]
+        yin = m[3] * xs + m[4] * ys + m[5]
+        inside = (xin >= 0) & (xin < W) & (yin >= 0) & (yin < H)          # made before any conversion to an integer
+    xin, yin = np.where(inside, xin, 0.5) - 0.5, np.where(inside, yin, 0.5) - 0.5
+    fx, fy = np.floor(xin), np.floor(yin)
+    dx, dy = (xin - fx)[..., None], (yin - fy)[..., None]
+    x0, y0 = fx.astype(np.int64) - 1, fy.astype(np.int64) - 1
+    xi = [np.clip(x0 + k, 0, W - 1) for k in range(4)]
+    yi = [np.clip(y0 + k, 0, H - 1) for k in range(4)]
+    src = image.astype(np.float64)
+    rows = [_cubic(src[yi[j], xi[0]], src[yi[j], xi[1]], src[yi[j], xi[2]], src[yi[j], xi[3]], dx) for j in range(4)]
+    v = _cubic(rows[0], rows[1], rows[2], rows[3], dy)
+    out = np.where(v <= 0.0, 0.0, np.where(v >= 255.0, 255.0, v)).astype(np.uint8)
+    out[~inside] = 0
+    return out
+
+
+def _identity_targets(names):
+    """finetune.py:146-148 (LightCNNTrainer.targets_from_names): the class of an image is the number its name begins with, from 1."""
+    try:
+        return torch.tensor([int(os.path.basename(n)[:3]) - 1 for n in names], dtype=torch.int64)
+    except ValueError:
+        raise ValueError("every file name must begin with its three-digit identity (finetune.py:147 reads int(name[:3]))")
+
+
+class IdentityBatch(dict):
+    """A batch of LightCNN fine-tuning: {"img": [B, 1, H, W] or [B, 1, 128, 128], "target": int64 [B]} -- what LightCNNTrainer.step
+    and .capture take -- with .input_path, .batch_weight and .invalid as FaceBatch has them."""
+
+    def __init__(self, tensors, input_path, batch_weight, invalid=None):
+        dict.__init__(self, tensors)
+        self.input_path, self.batch_weight, self.invalid = input_path, batch_weight, invalid
+
+
+class IdentityStore(object):
+    """The preloaded set of lightcnn/dataset.py's ImgDataset as tensors on one device: images uint8 [N, H, W, 3], targets int64 [N]
+    (see the module's text).  Build it with from_arrays / from_directory / from_face_store / load."""
+
+    def __init__(self, tensors, names, isval, gallery_names, host=None):
+        self.t = tensors                      # images, targets
+        self.names = list(names)
+        self.isval = bool(isval)
+        self.gallery_names = list(gallery_names) if gallery_names is not None else None
+        self.host = host if host is not None else self
+        self.device = tensors["images"].device
+
+    # ------------------------------------------------------------------ construction
+    @classmethod
+    def from_arrays(cls, images, names, isval=False, gallery_list=None):
+        """images uint8 [N, H, W, 3] (RGB) in the order of `names`.  gallery_list: the names of gallery_list.npy, or None for the
+        reference's rule (the first *051_06.png per name[:3]); a training set has no gallery."""
+        images = torch.as_tensor(np.asarray(images) if not torch.is_tensor(images) else images)
+        if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
+            raise ValueError("images must be uint8 [N, H, W, 3], got %s %s" % (images.dtype, tuple(images.shape)))
+        return cls._from_tensor(images.contiguous().cpu(), names, isval, gallery_list)
+
+    @classmethod
+    def _from_tensor(cls, images, names, isval, gallery_list):
+        names = [str(n) for n in names]
+        if len(names) != images.shape[0] or len(set(names)) != len(names):
+            raise ValueError("need one distinct name per image (%d names, %d images)" % (len(names), images.shape[0]))
+        gallery = None
+        if isval:
+            if gallery_list is not None:
+                gallery = [str(g) for g in gallery_list]
+            else:
+                first = {}
+                for k in names:
+                    if k[:3] not in first and k.strip().endswith("051_06.png"):
+                        first[k[:3]] = k
+                gallery = list(first.values())
+            known = set(names)
+            missing = [g for g in gallery if g not in known]
+            if missing:
+                raise KeyError("gallery file %s is not among the images" % missing[0])
+        return cls({"images": images, "targets": _identity_targets(names)}, names, isval, gallery)
+
+    @classmethod
+    def from_directory(cls, dataroot, isval=False, threads=8):
+        """<dataroot>/{train,test}/images (and an optional gallery_list.npy beside a test set's images/), read once with PIL on
+        `threads` threads, the names sorted.  8-bit RGB files are taken byte for byte; anything else is refused."""
+        from concurrent.futures import ThreadPoolExecutor
+        from PIL import Image
+        base = os.path.join(dataroot, "test" if isval else "train")
+        names = sorted(os.listdir(os.path.join(base, "images")))
+
+        def read(name):
+            with Image.open(os.path.join(base, "images", name)) as im:
+                if im.mode != "RGB":
+                    raise ValueError("images/%s is stored as PIL mode %r; only 8-bit RGB files are read (byte for byte)" % (name, im.mode))
+                return np.asarray(im, dtype=np.uint8)
+
+        with ThreadPoolExecutor(max_workers=max(1, int(threads))) as ex:
+            arrs = list(ex.map(read, names))
+        if any(a.shape != arrs[0].shape for a in arrs):
+            raise ValueError("the files of images/ differ in size")
+        gallery_list = None
+        if isval and os.path.exists(os.path.join(base, "gallery_list.npy")):
+            gallery_list = [str(g) for g in np.load(os.path.join(base, "gallery_list.npy"))]
+        return cls.from_arrays(np.stack(arrs), names, isval, gallery_list)
+
+    @classmethod
+    def from_face_store(cls, store):
+        """The images of a FaceStore as an IdentityStore on the same device: the image tensors are SHARED, nothing is copied."""
+        h = store.host
+        host = cls._from_tensor(h.t["images"], h.names, h.isval, h.gallery_names if h.isval else None)
+        if store.device.type == "cpu":
+            return host
+        return cls({"images": store.t["images"], "targets": host.t["targets"].to(store.device)}, host.names, host.isval,
+                   host.gallery_names, host=host)
+
+    def save(self, path):
+        """The store as one uncompressed .npz."""
+        h = self.host
+        np.savez(path, images=h.t["images"].numpy(), targets=h.t["targets"].numpy(), names=np.array(h.names),
+                 gallery_names=np.array(h.gallery_names if h.gallery_names is not None else [], dtype=str),
+                 meta=np.array([str(int(h.isval)), str(int(h.gallery_names is not None))]))
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            meta = [str(m) for m in z["meta"]]
+            gallery = [str(g) for g in z["gallery_names"]] if meta[1] == "1" else None
+            return cls({"images": torch.from_numpy(z["images"]), "targets": torch.from_numpy(z["targets"])},
+                       [str(n) for n in z["names"]], meta[0] == "1", gallery)
+
+    def to(self, device):
+        """The store with its tensors on `device` (uploaded once); the CPU store stays behind it as .host."""
+        device = torch.device(device)
+        if device == self.device:
+            return self
+        if device.type == "cpu":
+            return self.host
+        h = self.host
+        return IdentityStore({k: v.to(device) for k, v in h.t.items()}, h.names, h.isval, h.gallery_names, host=h)
+
+    def __len__(self):
+        return self.t["images"].shape[0]
+
+    def nbytes(self):
+        return sum(v.numel() * v.element_size() for v in self.t.values())
+
+    # ------------------------------------------------------------------ the reference's dataset
+    def host_item(self, index, angle=None, flip=False, crop=False, matrix=None):
+        """Item `index` on the CPU as get_train_item / get_test_item and postprocess compute it (dataset.py:33-67): `angle` (degrees)
+        or `matrix` (rotation_matrix's six numbers; it wins over `angle`) and `flip` are the draws of RandomRotation and
+        RandomHorizontalFlip; with neither, the test item.  -> {"img": [1, H, W] or [1, 128, 128], "input_path", "target"}."""
+        h = self.host
+        if not 0 <= index < len(h):
+            raise IndexError("item %d of %d" % (index, len(h)))
+        img = h.t["images"][index].numpy()
+        H, W, _ = img.shape
+        if matrix is None and angle is not None:
+            matrix = rotation_matrix(float(angle), W, H)
+        if matrix is not None:
+            img = rotate_bicubic(img, matrix)                  # RandomRotation(5, resample=Image.BICUBIC, expand=False)
+        if flip:
+            img = img[:, ::-1, :]                              # RandomHorizontalFlip
+        img = torch.from_numpy(img.transpose((2, 0, 1)).copy()).float().div(255)          # ToTensor / .float().div(255)
+        img = torch.mean(img, dim=(0, ), keepdim=True)
+        if crop:
+            img = img[:, CROP_ROWS, CROP_COLS]
+            img = torch.nn.functional.interpolate(img.unsqueeze(0), (128, 128), mode="bilinear")
+            img = img[0]
+        return {"img": img, "input_path": h.names[index], "target": h.t["targets"][index].clone()}
+
+    def host_batch(self, indices, angles=None, flips=None, crop=False, matrices=None):
+        """The default collate of host_item over `indices` (with one angle or matrix and one flip per item, or none: test items):
+        {"img": [B, ...], "target": int64 [B], "input_path": list}."""
+        items = [self.host_item(int(i), None if angles is None else float(angles[j]), False if flips is None else bool(flips[j]), crop,
+                                None if matrices is None else [float(v) for v in matrices[j]]) for j, i in enumerate(indices)]
+        return {"img": torch.stack([it["img"] for it in items]), "target": torch.stack([it["target"] for it in items]),
+                "input_path": [it["input_path"] for it in items]}
+
+    def batch(self, index, matrix=None, flip=None, crop=False, out=None):
+        """-> {"img", "target", "invalid"} of the batch of `index` (int32 [B]) under `matrix` (float64 [B, 6]) and `flip` (uint8 [B]),
+        all on the store's device (lists will do on a CPU store); both None: test items.  One launch of ops.identity_batch on a
+        device store, host_batch on a CPU store.  `out`: destinations written in place."""
+        if self.device.type == "cuda":
+            from . import ops
+            return ops.identity_batch(self.t["images"], self.t["targets"], index, matrix, flip, crop=crop, out=out)
+        as_list = lambda v: v.tolist() if torch.is_tensor(v) else (None if v is None else list(v))          # noqa: E731
+        idx = as_list(index)
+        res = self.host_batch(idx, None, as_list(flip), crop, as_list(matrix))
+        del res["input_path"]
+        res["invalid"] = torch.zeros(len(idx), dtype=torch.int32)
+        if out is not None:
+            for k, v in res.items():
+                if out.get(k) is not None:
+                    res[k] = out[k].copy_(v)
+        return res
+
+    # ------------------------------------------------------------------ the gallery (as FaceStore has it)
+    def gallery_rows(self):
+        if self.gallery_names is None:
+            raise ValueError("only a test set has a gallery")
+        row = {n: i for i, n in enumerate(self.names)}
+        return [row[g] for g in self.gallery_names]
+
+    host_gallery = FaceStore.host_gallery
+    gallery = FaceStore.gallery
+
+
+class IdentityLoader(object):
+    """The reference's DataLoader over an IdentityStore (finetune.py:98-106: shuffle=True for training, sequential for validation,
+    drop_last=False): iterating yields one IdentityBatch per step.
+
+    Epoch e draws, under ONE generator seeded with seed + e and in this order, the permutation (torch.randperm), the angles (float64,
+    uniform in [-degrees, degrees]: RandomRotation(degrees)) and the flips (probability 0.5), one angle and one flip per position of
+    the epoch.  The reference draws both from Python's global `random` inside its loader workers, so its own sequence cannot be
+    reproduced; the distributions are the same.  The matrices are built on the host (rotation_matrix); index, matrices and flips are
+    uploaded once per epoch and a step is one launch on slices of them.  A validation store yields un-augmented batches.  `out` and
+    the two alternating buffer sets work as FaceLoader's do; a short last batch is written into the leading rows of its buffers."""
+
+    def __init__(self, store, batch_size, crop=False, shuffle=None, drop_last=False, seed=0, out=None, degrees=5.0):
+        if batch_size < 1:
+            raise ValueError("batch_size must be positive")
+        if not degrees >= 0:
+            raise ValueError("degrees must not be negative")
+        self.store, self.batch_size, self.crop, self.drop_last = store, int(batch_size), bool(crop), bool(drop_last)
+        self.seed, self.degrees = int(seed), float(degrees)
+        self.shuffle = (not store.isval) if shuffle is None else bool(shuffle)
+        self.augment = not store.isval
+        self.epoch = 0
+        self.out = out
+        self._sets = [dict(out)] if out is not None else None
+
+    def __len__(self):
+        n, B = len(self.store), self.batch_size
+        return n // B if self.drop_last else (n + B - 1) // B
+
+    def draws(self, epoch):
+        """-> (permutation int32 [n], angles float64 [n], flips uint8 [n]) of `epoch`, on the host; position i of the epoch shows item
+        permutation[i] rotated by angles[i] and mirrored where flips[i] (a validation store: angles and flips are None)."""
+        n = len(self.store)
+        g = torch.Generator().manual_seed(self.seed + epoch)
+        perm = torch.randperm(n, generator=g).to(torch.int32) if self.shuffle else torch.arange(n, dtype=torch.int32)
+        if not self.augment:
+            return perm, None, None
+        angles = (torch.rand(n, dtype=torch.float64, generator=g) * 2.0 - 1.0) * self.degrees
+        flips = (torch.rand(n, generator=g) < 0.5).to(torch.uint8)
+        return perm, angles, flips
+
+    def permutation(self, epoch):
+        return self.draws(epoch)[0]
+
+    def matrices(self, angles):
+        """float64 [n, 6]: rotation_matrix of every angle for the store's image size."""
+        _, H, W, _ = self.store.t["images"].shape
+        return torch.tensor([rotation_matrix(a, W, H) for a in angles.tolist()], dtype=torch.float64).view(-1, 6)
+
+    def _destinations(self, step, b):
+        if self.store.device.type != "cuda":
+            return self.out if (self.out is None or b == self.batch_size) else {k: v[:b] for k, v in self.out.items()}
+        if self._sets is None:
+            self._sets = [{}, {}]
+        dst = self._sets[step % len(self._sets)]
+        return dst if b == self.batch_size else {k: v[:b] for k, v in dst.items()}
+
+    def __iter__(self):
+        store, B = self.store, self.batch_size
+        perm, angles, flips = self.draws(self.epoch)
+        self.epoch += 1
+        index = perm.to(store.device)          # the uploads of the epoch
+        matrix = self.matrices(angles).to(store.device) if self.augment else None
+        flip = flips.to(store.device) if self.augment else None
+        order = perm.tolist()
+        names = store.host.names
+        n = len(store)
+        for step in range(len(self)):
+            lo, hi = step * B, min(n, step * B + B)
+            dst = self._destinations(step, hi - lo)
+            res = store.batch(index[lo:hi], matrix[lo:hi] if self.augment else None, flip[lo:hi] if self.augment else None,
+                              self.crop, out=dst)
+            if store.device.type == "cuda" and hi - lo == B:
+                self._sets[step % len(self._sets)].update(res)          # buffers the first full batch allocated are kept
+            invalid = res.pop("invalid")
+            yield IdentityBatch(res, [names[i] for i in order[lo:hi]], hi - lo, invalid)

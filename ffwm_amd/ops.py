@@ -1329,3 +1329,53 @@ def face_batch(images, pairs, index, masks=None, pair_lm=None, lm=None, lm_flip=
                 _ptr(res.get("lm_F")), _ptr(res.get("gate")), _ptr(res["invalid"]), N, H, W, P, K, KG, L, B, int(train), stream),
                 "ffwm_face_batch")
     return res
+
+
+# ---------------------------------------------------------------- LightCNN fine-tuning batches
+def identity_batch(images, targets, index, matrix=None, flip=None, crop=False, out_side=128, out=None):
+    """One batch of the reference's lightcnn ImgDataset from a device-resident store in ONE launch (csrc/identity_batch.hip): images
+    uint8 [N, H, W, 3], targets int64 [N], index int32 [B] ON THE DEVICE -> {"img": float32 [B, 1, H, W] ([B, 1, out_side, out_side]
+    with `crop`), "target": int64 [B], "invalid": int32 [B]}.  With matrix float64 [B, 6] and flip uint8 [B] a training batch (PIL's
+    bicubic rotation under those inverse-map matrices, then the mirror); without them a test batch (byte / 255 and the channel mean).
+    `out`: a dict of destinations of those shapes, written in place (a missing one is allocated).  No host-device copy and no
+    synchronisation: an index out of range or a matrix that is not finite gives zeros, target 0 and invalid[b] = 1."""
+    name = "identity_batch"
+    augment = matrix is not None or flip is not None
+    if augment and (matrix is None or flip is None):
+        raise ValueError("%s: an augmented batch needs both matrix and flip" % name)
+    if not images.is_cuda:
+        raise NotImplementedError("%s: ffwm_amd ops run on the GPU only (got a %s tensor); IdentityStore.host_batch is the CPU path"
+                                  % (name, images.device))
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3 or not images.is_contiguous():
+        raise ValueError("%s: images must be contiguous uint8 [N, H, W, 3]" % name)
+    tables = (("targets", targets, torch.int64), ("index", index, torch.int32)) + (
+        (("matrix", matrix, torch.float64), ("flip", flip, torch.uint8)) if augment else ())
+    for key, t, dt in tables:
+        if t.dtype != dt or t.device != images.device or not t.is_contiguous():
+            raise ValueError("%s: %s must be a contiguous %s tensor on %s" % (name, key, dt, images.device))
+    N, H, W, _ = images.shape
+    if tuple(targets.shape) != (N,) or index.dim() != 1:
+        raise ValueError("%s: targets must be [%d] and index [B]" % (name, N))
+    B = index.shape[0]
+    if augment and (tuple(matrix.shape) != (B, 6) or tuple(flip.shape) != (B,)):
+        raise ValueError("%s: matrix must be [%d, 6] and flip [%d]" % (name, B, B))
+    crop, out_side = bool(crop), int(out_side)
+    if crop and (H <= 30 or W <= 30 or out_side < 1):
+        raise ValueError("%s: crop takes [28:-2, 15:-15] of the plane (H and W must exceed 30) and a positive out_side" % name)
+    side = (out_side, out_side) if crop else (H, W)
+    shapes = {"img": ((B, 1) + side, torch.float32), "target": ((B,), torch.int64), "invalid": ((B,), torch.int32)}
+    res = {}
+    for key, (shape, dt) in shapes.items():
+        t = None if out is None else out.get(key)
+        if t is None:
+            t = torch.empty(shape, dtype=dt, device=images.device)
+        elif tuple(t.shape) != shape or t.dtype != dt or t.device != images.device or not t.is_contiguous():
+            raise ValueError("%s: the destination %s must be a contiguous %s tensor of shape %s on %s" % (name, key, dt, shape, images.device))
+        res[key] = t
+    if B:
+        with _on_device(images) as stream:
+            _lib.check(_lib.load().ffwm_identity_batch(
+                _ptr(images), _ptr(targets), _ptr(index), _ptr(matrix) if augment else None, _ptr(flip) if augment else None,
+                _ptr(res["img"]), _ptr(res["target"]), _ptr(res["invalid"]), N, H, W, B, out_side, int(augment), int(crop), stream),
+                "ffwm_identity_batch")
+    return res

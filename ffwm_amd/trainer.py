@@ -1447,6 +1447,25 @@ class LightCNNTrainer(object):
     def loss_values(self):
         return {k: float(v.detach()) for k, v in self.losses.items()}
 
+    def train_epoch(self, loader, epoch):
+        """train() (finetune.py:131-187) behind adjust_learning_rate(epoch) (finetune.py:116): one step per batch of `loader` (an
+        IdentityLoader, or any iterable of {"img", "target"}) -> (loss, prec@1, prec@5) as the reference's AverageMeters give them: the
+        means over the epoch weighted by the batch sizes, summed in float64.  The sums stay on the device and are read back once, at
+        the end.  Works eagerly and with a captured step (whose batches must all have the captured size: drop_last=True)."""
+        self.adjust_learning_rate(epoch)
+        sums, count = torch.zeros(3, dtype=torch.float64, device=self.device), 0
+        for batch in loader:
+            n = batch["img"].shape[0]
+            if self._graphs is not None and n != self._static.tensors["img"].shape[0]:
+                raise ValueError("LightCNNTrainer.train_epoch: the captured step takes batches of %d, got one of %d (drop_last=True "
+                                 "leaves the short last batch out)" % (self._static.tensors["img"].shape[0], n))
+            out = self.step(batch)
+            sums += torch.stack([out[k].detach().reshape(()).to(torch.float64) for k in ("loss", "prec1", "prec5")]) * n
+            count += n
+        if not count:
+            raise ValueError("LightCNNTrainer.train_epoch: the loader gave no batch")
+        return tuple(s / count for s in sums.tolist())          # (divided on the host: a device division by a scalar multiplies by 1 / count)
+
     def adjust_learning_rate(self, epoch):
         """finetune.py:283-291: every group's rate times 0.457305051927326 at epochs 25, 50, ...  -> the rates, one per group.  A
         captured step sees the new rates from its next replay (step() calls FlatSGD.sync_lr)."""

@@ -729,6 +729,26 @@ int ffwm_face_batch(const void* images, const void* masks, const void* pairs, co
 /* Gallery planes: out float32 [G, 1, H, W] = ((r + g) + b) / 3 of byte / 255 of image rows[g] (int32 [G], device) -- the arithmetic
  * of ffwm_identity_input (crop 0) on the float image.  A row outside [0, N) gives a plane of zeros.  Same argument checks. */
 int ffwm_face_gallery(const void* images, const void* rows, void* out, int64_t N, int64_t H, int64_t W, int64_t G, void* stream);
+/* LightCNN fine-tuning batches (csrc/identity_batch.hip): the reference's lightcnn/dataset.py with --preload in ONE launch.
+ *   images uint8 [N, H, W, 3], targets int64 [N], index int32 [B], matrix float64 [B, 6], flip uint8 [B]: all on the device (a
+ *   captured launch follows the contents of index, matrix and flip).
+ * augment 1 (a training item): image index[b] rotated as PIL's Image.rotate(angle, BICUBIC, expand=False) rotates it under the
+ *   inverse-map matrix[b] (xin = m0 (x + .5) + m1 (y + .5) + m2, yin = m3 .. m5; outside the image 0; the a = -1 cubic over 4 x 4
+ *   index-clamped taps in float64, clipped and truncated to a byte), mirrored along W where flip[b] != 0, byte / 255 in float32,
+ *   channel mean ((r + g) + b) / 3.  augment 0 (a test item): byte / 255 and the mean only; matrix and flip are not looked at (NULL
+ *   allowed).
+ * crop 1: the slice [28:-2, 15:-15] of that plane resized to out_side x out_side as upsample_bilinear2d (align_corners false) in
+ *   float32.  crop 0: out_side is not looked at.
+ * Written: img float32 [B, 1, H, W] (crop 0) or [B, 1, out_side, out_side] (crop 1), target int64 [B] = targets[index[b]], invalid
+ *   int32 [B]; every element exactly once by a plain store, nothing else.  A sample whose index is outside [0, N) or, with augment,
+ *   whose matrix has an entry that is not finite is never used as an address: zeros, target 0, invalid[b] = 1 (else 0).  Any finite
+ *   matrix is safe: the inside test is made before a coordinate becomes an integer.
+ * Before any launch: FFWM_ERR_ARG for a NULL pointer that the mode needs, a size <= 0, augment or crop outside {0, 1}, crop with
+ *   H <= 30 or W <= 30; FFWM_ERR_SIZE for H, W or out_side > 8192, B > 65535, N >= 2^31, or a crop whose band of 8 output rows reads
+ *   more than 64 KiB of plane rows. */
+int ffwm_identity_batch(const void* images, const void* targets, const void* index, const void* matrix, const void* flip, void* img,
+                        void* target, void* invalid, int64_t N, int64_t H, int64_t W, int64_t B, int64_t out_side, int augment,
+                        int crop, void* stream);
 
 /* ---- built-in per-kernel timing (HIP events on the launch stream) ---------------------------
  * ffwm_prof_enable(1) brackets every kernel launch of this library with a pair of HIP events
