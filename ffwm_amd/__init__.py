@@ -23,7 +23,8 @@ csyxwei/FFWM: hand-written HIP kernels behind the reference's own operator API.
     ffwm_amd.FaceStore           the reference's FaceDataset with --preload, kept on the device as bytes (ffwm_amd.data: from_directory /
                                  from_arrays / .npz, pairs, s2f, the gallery, host_item / host_batch as the CPU path), and
     ffwm_amd.FaceLoader          its DataLoader: one uploaded permutation per epoch, one gather launch per batch (csrc/face_batch.hip),
-                                 batches in the form the trainers' step() and capture() take
+                                 batches in the form the trainers' step() and capture() take; rotation=True on both is the random
+                                 rotation of --aug as a stated algorithm (cv2.warpAffine's fixed-point path; no OpenCV confirmed it)
     ffwm_amd.IdentityStore       the reference's lightcnn ImgDataset with --preload on the device (bytes and classes), and
     ffwm_amd.IdentityLoader      its DataLoader: PIL's bicubic RandomRotation(5), the flip, the channel mean and --crop of a whole batch
                                  in one launch (csrc/identity_batch.hip); LightCNNTrainer.train_epoch(loader, epoch) runs an epoch

@@ -96,6 +96,9 @@ _SIGNATURES = {
     # (images, masks, pairs, pair_lm, lm, lm_flip, gate, index; img_S, img_F, mask_S, mask_F, lm_S, lm_F, gate_out, invalid;
     #  N, H, W, P, K, KG, L, B; train, stream)
     "ffwm_face_batch": [_p] * 16 + [_i64] * 8 + [_i, _p],
+    # (the 8 inputs of ffwm_face_batch, lm_raw, lm_raw_flip, slot, xtab, ytab, cs; its 8 outputs; N, H, W, P, K, KG, L, B, A, load_size;
+    #  train, stream)
+    "ffwm_face_batch_aug": [_p] * 22 + [_i64] * 10 + [_i, _p],
     "ffwm_face_gallery": [_p, _p, _p] + [_i64] * 4 + [_p],
     # (images, targets, index, matrix, flip; img, target, invalid; N, H, W, B, out_side; augment, crop, stream)
     "ffwm_identity_batch": [_p] * 8 + [_i64] * 5 + [_i, _i, _p],

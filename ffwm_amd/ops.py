@@ -1285,6 +1285,20 @@ def face_batch(images, pairs, index, masks=None, pair_lm=None, lm=None, lm_flip=
     name = "face_batch"
     train = masks is not None
     tables = {"pairs": pairs, "index": index, "masks": masks, "pair_lm": pair_lm, "lm": lm, "lm_flip": lm_flip, "gate": gate}
+    (N, H, W, P, K, KG, L, B), res = _face_batch_plan(name, images, tables, train, out)
+    if B:
+        with _on_device(images) as stream:
+            _lib.check(_lib.load().ffwm_face_batch(
+                _ptr(images), _ptr(masks), _ptr(pairs), _ptr(pair_lm), _ptr(lm), _ptr(lm_flip), _ptr(gate), _ptr(index),
+                _ptr(res["img_S"]), _ptr(res["img_F"]), _ptr(res.get("mask_S")), _ptr(res.get("mask_F")), _ptr(res.get("lm_S")),
+                _ptr(res.get("lm_F")), _ptr(res.get("gate")), _ptr(res["invalid"]), N, H, W, P, K, KG, L, B, int(train), stream),
+                "ffwm_face_batch")
+    return res
+
+
+def _face_batch_plan(name, images, tables, train, out):
+    """The checks of face_batch / face_batch_aug on the store's tables -> ((N, H, W, P, K, KG, L, B), the destinations)."""
+    pairs, index, masks, pair_lm, lm, lm_flip, gate = (tables[k] for k, _ in _FACE_TABLES)
     if train and any(v is None for v in tables.values()):
         raise ValueError("%s: a training batch needs masks, pair_lm, lm, lm_flip and gate" % name)
     if not images.is_cuda:
@@ -1321,13 +1335,37 @@ def face_batch(images, pairs, index, masks=None, pair_lm=None, lm=None, lm_flip=
         elif tuple(t.shape) != shape or t.dtype != dt or t.device != images.device or not t.is_contiguous():
             raise ValueError("%s: the destination %s must be a contiguous %s tensor of shape %s on %s" % (name, key, dt, shape, images.device))
         res[key] = t
+    return (N, H, W, P, K, KG, L, B), res
+
+
+def face_batch_aug(images, pairs, index, masks, pair_lm, lm, lm_flip, gate, lm_raw, lm_raw_flip, slot, xtab, ytab, cs, load_size,
+                   out=None):
+    """face_batch's training batch with the S side rotated by a whole angle per sample, in ONE launch (ffwm_face_batch_aug in
+    csrc/face_batch.hip: the rotation of the reference's --aug, stated as cv2.warpAffine's fixed-point bilinear path -- see
+    ffwm_amd/data.py; no OpenCV was at hand to confirm its bytes).  Beside face_batch's arguments: lm_raw / lm_raw_flip float32
+    [K, L, 2], slot int32 [B] ON THE DEVICE (the angle slot of every sample), xtab int32 [A, 2, W], ytab int32 [A, 2, H] and cs
+    float32 [A, 2] (data.FaceRotation makes them), A <= 64.  img_S, mask_S and lm_S change; an index or a slot out of range gives
+    zeros and invalid[b] = 1."""
+    name = "face_batch_aug"
+    tables = {"pairs": pairs, "index": index, "masks": masks, "pair_lm": pair_lm, "lm": lm, "lm_flip": lm_flip, "gate": gate}
+    (N, H, W, P, K, KG, L, B), res = _face_batch_plan(name, images, tables, True, out)
+    if not torch.is_tensor(xtab) or xtab.dim() != 3:
+        raise ValueError("%s: xtab must be an int32 tensor [A, 2, %d]" % (name, W))
+    for key, t, dt, shape in (("lm_raw", lm_raw, torch.float32, (K, L, 2)), ("lm_raw_flip", lm_raw_flip, torch.float32, (K, L, 2)),
+                              ("slot", slot, torch.int32, (B,)), ("xtab", xtab, torch.int32, (xtab.shape[0], 2, W)),
+                              ("ytab", ytab, torch.int32, (xtab.shape[0], 2, H)), ("cs", cs, torch.float32, (xtab.shape[0], 2))):
+        if t.dtype != dt or t.device != images.device or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise ValueError("%s: %s must be a contiguous %s tensor of shape %s on %s" % (name, key, dt, shape, images.device))
+    A = xtab.shape[0]
+    if not 1 <= A <= 64 or load_size < 1:
+        raise ValueError("%s: 1 to 64 angle slots and a positive load_size" % name)
     if B:
         with _on_device(images) as stream:
-            _lib.check(_lib.load().ffwm_face_batch(
-                _ptr(images), _ptr(masks), _ptr(pairs), _ptr(pair_lm), _ptr(lm), _ptr(lm_flip), _ptr(gate), _ptr(index),
-                _ptr(res["img_S"]), _ptr(res["img_F"]), _ptr(res.get("mask_S")), _ptr(res.get("mask_F")), _ptr(res.get("lm_S")),
-                _ptr(res.get("lm_F")), _ptr(res.get("gate")), _ptr(res["invalid"]), N, H, W, P, K, KG, L, B, int(train), stream),
-                "ffwm_face_batch")
+            _lib.check(_lib.load().ffwm_face_batch_aug(
+                _ptr(images), _ptr(masks), _ptr(pairs), _ptr(pair_lm), _ptr(lm), _ptr(lm_flip), _ptr(gate), _ptr(index), _ptr(lm_raw),
+                _ptr(lm_raw_flip), _ptr(slot), _ptr(xtab), _ptr(ytab), _ptr(cs), _ptr(res["img_S"]), _ptr(res["img_F"]),
+                _ptr(res["mask_S"]), _ptr(res["mask_F"]), _ptr(res["lm_S"]), _ptr(res["lm_F"]), _ptr(res["gate"]), _ptr(res["invalid"]),
+                N, H, W, P, K, KG, L, B, A, int(load_size), 1, stream), "ffwm_face_batch_aug")
     return res
 
 

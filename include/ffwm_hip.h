@@ -726,6 +726,30 @@ int ffwm_face_batch(const void* images, const void* masks, const void* pairs, co
                     const void* gate, const void* index, void* img_S, void* img_F, void* mask_S, void* mask_F, void* lm_S, void* lm_F,
                     void* gate_out, void* invalid, int64_t N, int64_t H, int64_t W, int64_t P, int64_t K, int64_t KG, int64_t L,
                     int64_t B, int train, void* stream);
+/* The same training batch with the S side rotated: the random rotation of the reference's --aug (face_dataset.py:110-130) by a whole
+ * angle per sample, STATED as the classic bilinear path of cv2.warpAffine (no OpenCV was at hand to confirm its bytes).  Beside the
+ * arguments of ffwm_face_batch:
+ *   lm_raw / lm_raw_flip float32 [K, L, 2]: the landmark rows before .long() (plain, and after x -> 127 - x), row for row beside lm;
+ *   slot int32 [B] (device): the angle slot of every sample, in [0, A);  A in [1, 64];
+ *   xtab int32 [A, 2, W]: adelta[x] = rint(M0 x 1024), bdelta[x] = rint(M3 x 1024);  ytab int32 [A, 2, H]: X0[y] = rint((M1 y + M2)
+ *   1024) + 16, Y0[y] = rint((M4 y + M5) 1024) + 16 of warpAffine's inverted matrix M, made on the host once per angle and size;
+ *   cs float32 [A, 2]: cos and sin of -angle rounded to float32;  load_size: the centre of the landmark rotation is load_size / 2.
+ * Per pixel of img_S / mask_S: X = (X0[y] + adelta[x]) >> 5, Y = (Y0[y] + bdelta[x]) >> 5, S = the four taps at (Y >> 5, X >> 5) of
+ *   the (flipped, where index >= P) image under the weights (32 - fx)(32 - fy), fx (32 - fy), (32 - fx) fy, fx fy of fx = X & 31, fy =
+ *   Y & 31, a tap outside the image 0; img_S = float(S) / 1024 / 255 (exact up to the true division), mask_S = S > 0 ? 1 : 0.
+ * lm_S = the reference's float32 chain on the raw row: x0 = x - h, y0 = y - h (h = load_size / 2), x' = (x0 c - y0 s) + h, y' = (x0 s
+ *   + y0 c) + h, every product and sum rounded to float32 on its own, clipped to [0, load_size], truncated, clamped to load_size - 1.
+ * img_F, mask_F, lm_F, gate_out and the rule for invalid samples are those of ffwm_face_batch; a slot outside [0, A) is invalid too.
+ * One launch, every output element written once by a plain store, nothing else; the source rows a block needs are staged in LDS when
+ * they fit 32 KiB + 64 B and read from global memory otherwise.  Tables are only ever indexed inside their bounds and every tap is
+ * checked against the rows at hand: wrong table CONTENTS give wrong pixels, never an address outside the store.
+ * Before any launch: the checks of ffwm_face_batch, and FFWM_ERR_ARG for train != 1, a NULL pointer among the new ones, load_size <=
+ * 0, A < 1 or A > 64; FFWM_ERR_SIZE for load_size > 2^24. */
+int ffwm_face_batch_aug(const void* images, const void* masks, const void* pairs, const void* pair_lm, const void* lm,
+                        const void* lm_flip, const void* gate, const void* index, const void* lm_raw, const void* lm_raw_flip,
+                        const void* slot, const void* xtab, const void* ytab, const void* cs, void* img_S, void* img_F, void* mask_S,
+                        void* mask_F, void* lm_S, void* lm_F, void* gate_out, void* invalid, int64_t N, int64_t H, int64_t W, int64_t P,
+                        int64_t K, int64_t KG, int64_t L, int64_t B, int64_t A, int64_t load_size, int train, void* stream);
 /* Gallery planes: out float32 [G, 1, H, W] = ((r + g) + b) / 3 of byte / 255 of image rows[g] (int32 [G], device) -- the arithmetic
  * of ffwm_identity_input (crop 0) on the float image.  A row outside [0, N) gives a plane of zeros.  Same argument checks. */
 int ffwm_face_gallery(const void* images, const void* rows, void* out, int64_t N, int64_t H, int64_t W, int64_t G, void* stream);
