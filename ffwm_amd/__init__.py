@@ -28,6 +28,10 @@ csyxwei/FFWM: hand-written HIP kernels behind the reference's own operator API.
     ffwm_amd.IdentityStore       the reference's lightcnn ImgDataset with --preload on the device (bytes and classes), and
     ffwm_amd.IdentityLoader      its DataLoader: PIL's bicubic RandomRotation(5), the flip, the channel mean and --crop of a whole batch
                                  in one launch (csrc/identity_batch.hip); LightCNNTrainer.train_epoch(loader, epoch) runs an epoch
+    ffwm_amd.ResultWriter        the reference's result images (util/util.py tensor2im / tensor2mask / tensor2flow / tensor2att,
+                                 flow_util.flow2img, the Visualizer's routing and file names): a whole batch of visuals as uint8 RGB
+                                 sheets from one call (csrc/visuals.hip), one copy to the host, PNGs through PIL (ffwm_amd.visuals:
+                                 render, from_result, train_visuals, and the numpy restatements that are the CPU path)
 """
 __version__ = "0.1.0"
 
@@ -43,4 +47,7 @@ def __getattr__(name):
     if name in ("FaceStore", "FaceLoader", "FaceBatch", "IdentityStore", "IdentityLoader", "IdentityBatch"):
         from . import data
         return getattr(data, name)
+    if name == "ResultWriter":
+        from . import visuals
+        return visuals.ResultWriter
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

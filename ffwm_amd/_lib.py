@@ -102,6 +102,7 @@ _SIGNATURES = {
     "ffwm_face_gallery": [_p, _p, _p] + [_i64] * 4 + [_p],
     # (images, targets, index, matrix, flip; img, target, invalid; N, H, W, B, out_side; augment, crop, stream)
     "ffwm_identity_batch": [_p] * 8 + [_i64] * 5 + [_i, _i, _p],
+    "ffwm_visuals": [_p, _i, _p, _i64, _i, _p],               # (array of ffwm_visual_item, n, workspace, workspace_bytes, dtype, stream)
     "ffwm_prof_enable": [_i],
     "ffwm_prof_collect": [],
     "ffwm_prof_get": [_i, ctypes.c_char_p, _i, ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double),
@@ -118,7 +119,7 @@ EXPORTS = sorted(list(_SIGNATURES) + ["ffwm_last_error", "ffwm_conv3x3_winograd_
                                       "ffwm_conv2d_forward_workspace", "ffwm_guided_filter_workspace_bytes",
                                       "ffwm_sampling_correctness_workspace_bytes", "ffwm_landmark_loss_workspace_bytes",
                                       "ffwm_cosine_topk_workspace_bytes", "ffwm_softmax_xent_workspace_bytes",
-                                      "ffwm_conv3x3_wg_weights_bytes", "ffwm_conv3x3_wg_workspace_bytes"])
+                                      "ffwm_conv3x3_wg_weights_bytes", "ffwm_conv3x3_wg_workspace_bytes", "ffwm_visuals_workspace_bytes"])
 
 
 class FFWMError(RuntimeError):
@@ -159,6 +160,8 @@ def load():
     lib.ffwm_conv3x3_wg_weights_bytes.restype = _i64
     lib.ffwm_conv3x3_wg_workspace_bytes.argtypes = [_i64] * 5
     lib.ffwm_conv3x3_wg_workspace_bytes.restype = _i64
+    lib.ffwm_visuals_workspace_bytes.argtypes = [_p, _i]
+    lib.ffwm_visuals_workspace_bytes.restype = _i64
     lib.ffwm_last_error.argtypes = []
     lib.ffwm_last_error.restype = ctypes.c_char_p
     got = lib.ffwm_abi_version()

@@ -1417,3 +1417,62 @@ def identity_batch(images, targets, index, matrix=None, flip=None, crop=False, o
                 _ptr(res["img"]), _ptr(res["target"]), _ptr(res["invalid"]), N, H, W, B, out_side, int(augment), int(crop), stream),
                 "ffwm_identity_batch")
     return res
+
+
+# ---------------------------------------------------------------- result images (csrc/visuals.hip)
+class _VisualItem(ctypes.Structure):           # include/ffwm_hip.h: ffwm_visual_item
+    _fields_ = [("src", ctypes.c_void_p), ("palette", ctypes.c_void_p), ("out", ctypes.c_void_p), ("kind", ctypes.c_int),
+                ("B", ctypes.c_int64), ("C", ctypes.c_int64), ("H", ctypes.c_int64), ("W", ctypes.c_int64)]
+
+
+def visuals(items):
+    """items: up to 16 tuples (tensor [B, C, H, W], kind, palette or None) with kind 0 image / 1 mask / 2 flow / 3 palette (uint8
+    [256, 3] RGB on the device) -> a list of uint8 [B, H, W, 3] RGB sheets, one per item, written by ONE call (two launches with a
+    flow item, else one) as the reference's tensor2im / tensor2mask / tensor2flow / tensor2att write them on the host.  The sheets are
+    views of one allocation (16-byte aligned each), so they cross to the host in one copy.  Tensors are taken through
+    .float().contiguous(), as the reference calls .float()."""
+    name = "visuals"
+    if not items:
+        return []
+    if len(items) > 16:
+        raise ValueError("%s: at most 16 items per call, got %d" % (name, len(items)))
+    srcs, pals, offsets, total = [], [], [], 0
+    dev = items[0][0].device
+    for i, (t, kind, pal) in enumerate(items):
+        if not t.is_cuda:
+            raise NotImplementedError("%s: ffwm_amd ops run on the GPU only (got a %s tensor); ffwm_amd.visuals.render is the CPU path"
+                                      % (name, t.device))
+        if t.device != dev:
+            raise ValueError("%s: tensors live on different devices (%s vs %s)" % (name, t.device, dev))
+        if t.dim() != 4 or t.numel() == 0:
+            raise ValueError("%s: item %d: expected a non-empty 4-D NCHW tensor, got shape %s" % (name, i, tuple(t.shape)))
+        if kind == 3:
+            if pal is None:
+                raise ValueError("%s: item %d: a palette item needs its uint8 [256, 3] palette" % (name, i))
+            if not (pal.is_cuda and pal.device == dev and pal.dtype == torch.uint8 and tuple(pal.shape) == (256, 3)):
+                raise ValueError("%s: item %d: the palette must be a uint8 [256, 3] tensor on %s" % (name, i, dev))
+            pal = pal.contiguous()
+        else:
+            pal = None
+        srcs.append(t.detach().float().contiguous())
+        pals.append(pal)
+        offsets.append(total)
+        B, _, H, W = t.shape
+        total += (3 * B * H * W + 15) // 16 * 16
+    sheet = torch.empty(total, dtype=torch.uint8, device=dev)
+    arr = (_VisualItem * len(items))()
+    outs = []
+    for a, s, pal, off, (_, kind, _) in zip(arr, srcs, pals, offsets, items):
+        B, C, H, W = s.shape
+        out = sheet[off:off + 3 * B * H * W].view(B, H, W, 3)
+        a.src, a.palette, a.out, a.kind, a.B, a.C, a.H, a.W = s.data_ptr(), _ptr(pal), out.data_ptr(), int(kind), B, C, H, W
+        outs.append(out)
+    lib = _lib.load()
+    table = ctypes.cast(arr, ctypes.c_void_p)
+    nbytes = lib.ffwm_visuals_workspace_bytes(table, len(items))
+    if nbytes < 0:
+        _lib.check(int(nbytes), "ffwm_visuals_workspace_bytes")
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev) if nbytes else None
+    with _on_device(srcs[0]) as stream:
+        _lib.check(lib.ffwm_visuals(table, len(items), _ptr(ws), nbytes, _lib.F32, stream), "ffwm_visuals")
+    return outs

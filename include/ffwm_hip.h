@@ -32,6 +32,7 @@
  *   ffwm_softmax_xent               <- nn.CrossEntropyLoss + accuracy(output, target, (1, 5))  lightcnn/finetune.py:109,152-159
  *   ffwm_l1_multi                   <- the w * F.l1_loss(x * m, y * m) terms of backward_G   models/ffwm_model.py:107-139
  *   ffwm_conv2d_wgrad[_tiled]       <- convolution_backward grad_weight of the stride-2 / transposed / small-plane convs
+ *   ffwm_visuals                    <- tensor2im / tensor2mask / tensor2flow / tensor2att + flow2img   util/util.py:10-70, util/flow_util.py:23-153
  *
  * Conventions
  *   - dtype: FFWM_F32 or FFWM_F64 (the reference dispatches AT_DISPATCH_FLOATING_TYPES).
@@ -773,6 +774,37 @@ int ffwm_face_gallery(const void* images, const void* rows, void* out, int64_t N
 int ffwm_identity_batch(const void* images, const void* targets, const void* index, const void* matrix, const void* flip, void* img,
                         void* target, void* invalid, int64_t N, int64_t H, int64_t W, int64_t B, int64_t out_side, int augment,
                         int crop, void* stream);
+
+/* ---- result images (csrc/visuals.hip): the reference's util/util.py tensor2im / tensor2mask / tensor2flow / tensor2att and
+ * util/flow_util.py flow2img for whole batches, every visual of a call in one pass.  An item is one visual:
+ *   src      float32 [B, C, H, W], contiguous, 4-byte aligned (16-byte aligned with H*W % 4 == 0 takes the float4 path)
+ *   out      uint8 [B, H, W, 3], RGB in HWC order, 4-byte aligned; every byte written exactly once by a plain store, nothing else
+ *   palette  kind 3 only: uint8 [256, 3] RGB on the device (the library ships no colour map)
+ *   kind     0 IMAGE   C == 3: u8(x * 255);  C == 1: u8(((x - 0.5) * 2) * 255) on all three channels
+ *            1 MASK    u8(x * 255), C == 1 tiled to three channels; C is 1 or 3
+ *            2 FLOW    C == 2: g = clamp((f + 1) * (H / 2), 0, H - 1) in float32 (both axes scale with H; NaN passes), u = g[0] - x,
+ *                      v = g[1] - y, rad = sqrtf(u u + v v); per image m = max(rad), NaN if any cell is NaN, maxrad = m > -1 ? m : -1;
+ *                      u' = (double)(u / maxrad) + DBL_EPSILON (v' alike; float32 division, float64 from there on); a cell whose u' or
+ *                      v' is NaN is black; fk = (atan2(-v', -u') / pi + 1) / 2 * 54 + 1, k0 = floor(fk), k1 = k0 + 1 (56 -> 1),
+ *                      f = fk - k0; per channel col = (1 - f) wheel[k0 - 1] / 255 + f wheel[k1 - 1] / 255 over the 55-entry Middlebury
+ *                      wheel; rad' = sqrt(u' u' + v' v') <= 1: col = 1 - rad' (1 - col), else col *= 0.75; byte = floor(255 col)
+ *            3 PALETTE palette[u8(x[:, 0] * 255)], C >= 1
+ *   u8(t): truncate toward zero to int32, keep the low 8 bits; NaN, +-inf and |t| >= 2^31 give 0.
+ * Items may differ in size; at most 16 per call.  workspace: one float per image of the FLOW items (ffwm_visuals_workspace_bytes;
+ * NULL / 0 without one), written by a first launch (one workgroup per flow image, no atomics) and read by the colouring launch; a
+ * call without a flow item is one launch.  float32 only: any other dtype returns FFWM_ERR_DTYPE.
+ * Before any launch: FFWM_ERR_ARG for a NULL table, src or out, n outside 1 .. 16, a kind outside 0 .. 3, a C the kind does not
+ * take, a non-positive size, a palette item without palette, a misaligned pointer, a workspace that is missing or too small;
+ * FFWM_ERR_SIZE for B*H*W >= 2^31.  ffwm_visuals_workspace_bytes returns the same negative status for such a table. */
+typedef struct ffwm_visual_item {
+    const void* src;
+    const void* palette;
+    void* out;
+    int kind;
+    int64_t B, C, H, W;
+} ffwm_visual_item;
+int64_t ffwm_visuals_workspace_bytes(const ffwm_visual_item* items, int n);
+int ffwm_visuals(const ffwm_visual_item* items, int n, void* workspace, int64_t workspace_bytes, int dtype, void* stream);
 
 /* ---- built-in per-kernel timing (HIP events on the launch stream) ---------------------------
  * ffwm_prof_enable(1) brackets every kernel launch of this library with a pair of HIP events
