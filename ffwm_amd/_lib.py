@@ -89,6 +89,9 @@ _SIGNATURES = {
     "ffwm_conv3x3_wg_forward": [_p, _p, _p, _p, _p] + [_i64] * 5 + [_i, _p, _i, _p],
     "ffwm_conv3x3_wg_forward_tiled": [_p, _p, _p, _p, _p] + [_i64] * 5 + [_i, _p, _i, _i, _p],
     "ffwm_conv3x3_wg_tile": [_i64] * 5,
+    "ffwm_conv3x3_wg_split_weights": [_p, _p, _i64, _i64, _i, _p],
+    "ffwm_conv3x3_wg_split_forward": [_p, _p, _p, _p, _p] + [_i64] * 5 + [_i, ctypes.c_double, _i, _i, _p],
+    "ffwm_conv3x3_wg_split_tile": [_i64] * 5,
     "ffwm_mfm_tail_forward": [_p, _p, _p, _p] + [_i64] * 4 + [_i, _i, _p],
     "ffwm_identity_input": [_p, _p] + [_i64] * 4 + [_i, _i, _p],
     "ffwm_identity_input_backward": [_p, _p] + [_i64] * 4 + [_i, _i, _p],
@@ -119,7 +122,8 @@ EXPORTS = sorted(list(_SIGNATURES) + ["ffwm_last_error", "ffwm_conv3x3_winograd_
                                       "ffwm_conv2d_forward_workspace", "ffwm_guided_filter_workspace_bytes",
                                       "ffwm_sampling_correctness_workspace_bytes", "ffwm_landmark_loss_workspace_bytes",
                                       "ffwm_cosine_topk_workspace_bytes", "ffwm_softmax_xent_workspace_bytes",
-                                      "ffwm_conv3x3_wg_weights_bytes", "ffwm_conv3x3_wg_workspace_bytes", "ffwm_visuals_workspace_bytes"])
+                                      "ffwm_conv3x3_wg_weights_bytes", "ffwm_conv3x3_wg_workspace_bytes", "ffwm_visuals_workspace_bytes",
+                                      "ffwm_conv3x3_wg_split_weights_bytes", "ffwm_conv3x3_wg_split_workspace_bytes"])
 
 
 class FFWMError(RuntimeError):
@@ -160,6 +164,10 @@ def load():
     lib.ffwm_conv3x3_wg_weights_bytes.restype = _i64
     lib.ffwm_conv3x3_wg_workspace_bytes.argtypes = [_i64] * 5
     lib.ffwm_conv3x3_wg_workspace_bytes.restype = _i64
+    lib.ffwm_conv3x3_wg_split_weights_bytes.argtypes = [_i64, _i64]
+    lib.ffwm_conv3x3_wg_split_weights_bytes.restype = _i64
+    lib.ffwm_conv3x3_wg_split_workspace_bytes.argtypes = [_i64] * 5
+    lib.ffwm_conv3x3_wg_split_workspace_bytes.restype = _i64
     lib.ffwm_visuals_workspace_bytes.argtypes = [_p, _i]
     lib.ffwm_visuals_workspace_bytes.restype = _i64
     lib.ffwm_last_error.argtypes = []

@@ -18,23 +18,13 @@
 //
 // No atomics, no split of the reduction: one fma chain over C per M entry, bit-reproducible.  The roundings per entry are those of
 // conv_winograd.hip (two in V, four in U, the chain, four in the output transform): tests/conv_bounds.py rho_winograd, splits = 1.
-#include "common.hpp"
+#include "conv_winograd_gemm.hpp"
 
 namespace ffwm {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 enum { kWgNone = FFWM_WG_NONE, kWgBias = FFWM_WG_BIAS, kWgBiasRelu = FFWM_WG_BIAS_RELU, kWgBiasMfm = FFWM_WG_BIAS_MFM };
 constexpr int kWgStage = 16;             // input channels per LDS stage of the GEMM: four groups of four
-
-struct WgGeo {
-    int C, C4;               // input channels; groups of four channels of the padded Cp
-    int H, W, K;
-    int TH, TW, T;           // 2 x 2 output tiles per column / row / in total (B TH TW)
-    int Tp, Kp;              // T and K rounded up to the GEMM tile
-};
 
 // ATen's NaN rule, as csrc/mfm.hip has it: maximum(a, b) is NaN when either operand is, relu(NaN) is NaN
 __device__ __forceinline__ float wg_max_nan(float a, float b) { return __builtin_isunordered(a, b) ? a + b : fmaxf(a, b); }
@@ -235,21 +225,6 @@ wg_batched_gemm_kernel(const float* __restrict__ U, const float* __restrict__ V,
 // ---------------------------------------------------------------------------------------------------- output transform
 // One thread = one tile x one output channel (blockIdx.y; two channels, k and k + K / 2, under the max-feature-map epilogue): 16
 // loads per channel with the lanes along the tiles, y = At (M A), the epilogue, a 2 x 2 store (odd H / W: the pixels that exist).
-__device__ __forceinline__ void wg_tile_of(const float* __restrict__ M, size_t pstride, float bv, float (&y)[4]) {
-    float z[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float m0 = M[(i * 4 + 0) * pstride], m1 = M[(i * 4 + 1) * pstride], m2 = M[(i * 4 + 2) * pstride], m3 = M[(i * 4 + 3) * pstride];
-        z[i][0] = (m0 + m1) + m2;
-        z[i][1] = (m1 - m2) - m3;
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        y[j] = ((z[0][j] + z[1][j]) + z[2][j]) + bv;
-        y[2 + j] = ((z[1][j] - z[2][j]) - z[3][j]) + bv;
-    }
-}
-
 __global__ void __launch_bounds__(kBlock)
 wg_output_transform_kernel(const float* __restrict__ M, const float* __restrict__ bias, float* __restrict__ out, const WgGeo g, int epi,
                            int vec) {
@@ -270,31 +245,13 @@ wg_output_transform_kernel(const float* __restrict__ M, const float* __restrict_
 #pragma unroll
         for (int v = 0; v < 4; ++v) y[v] = wg_max_nan(y[v], y2[v]);
     }
-    const int per = g.TH * g.TW;
-    const int b = t / per, rem = t - b * per;
-    const int ty = rem / g.TW, tx = rem - ty * g.TW;
-    const int oy = 2 * ty, ox = 2 * tx;
-    const bool row1 = oy + 1 < g.H, col1 = ox + 1 < g.W;
-    float* o = out + ((static_cast<size_t>(b) * Kout + ko) * g.H + oy) * g.W + ox;
-    if (vec) {               // W even, 8-byte aligned output: every tile has both columns
-        *reinterpret_cast<float2*>(o) = make_float2(y[0], y[1]);
-        if (row1) *reinterpret_cast<float2*>(o + g.W) = make_float2(y[2], y[3]);
-    } else {
-        o[0] = y[0];
-        if (col1) o[1] = y[1];
-        if (row1) {
-            o[g.W] = y[2];
-            if (col1) o[g.W + 1] = y[3];
-        }
-    }
+    wg_store_tile(out, g, t, ko, Kout, y, vec);
 }
 
 }  // namespace
 }  // namespace ffwm
 
 using namespace ffwm;
-
-static int64_t wg_round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
 // The route of one call, decided once: the workspace query and the three launches read this plan.
 struct WgPlan {

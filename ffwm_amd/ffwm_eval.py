@@ -36,8 +36,19 @@ import torch.nn.functional as F
 from .graphs import GraphedForward
 
 LRELU, NONE, SIGMOID = 1, 0, 3
-KINDS = ("winograd", "conv_mfma", "vendor_conv", "bias_act", "add_act", "gate", "shuffle_bias_act", "image_head", "upsample2x",
+KINDS = ("winograd", "winograd_split", "conv_mfma", "vendor_conv", "bias_act", "add_act", "gate", "shuffle_bias_act", "image_head", "upsample2x",
          "warp_multi")
+
+PRECISIONS = ("fp32", "bf16x3")
+# A memory condition, not a tuned threshold: a layer whose split-route workspace (V and M of csrc/conv_winograd_gemm_split.hip) would
+# make the executor's arena hold more than this keeps its fp32 route (netG's 195-channel layers at 128 x 128, batch 8: over 400 MB).
+SPLIT_WORKSPACE_LIMIT = 256 << 20
+# netG layers that stay on their fp32 route under precision="bf16x3": those where the split route measured slower than the layer's
+# present route at BOTH batch 1 and batch 8 by more than the larger min-max spread (tools/split_conv_bench.py,
+# profiles/wino_gemm_split.txt) -- the rule identity_eval.VENDOR_LAYERS was made by.  The measurement names none: e0.2.blocks.0 / .3
+# (64 -> 64 at 128 x 128) are slower at batch 1 (34 against 23 us) and past SPLIT_WORKSPACE_LIMIT at batch 8, where the rule has nothing
+# to compare.
+SPLIT_EXCLUDED_LAYERS = frozenset()
 
 _Layer = collections.namedtuple("_Layer", "w b k stride pad")
 _Res = collections.namedtuple("_Res", "act slope inner_slope")
@@ -79,11 +90,65 @@ class _Spec(object):
         return n
 
 
-def conv_route(L, x, act):
+def check_precision(who, precision, backend):
+    if precision not in PRECISIONS:
+        raise ValueError("%s: precision must be one of %s" % (who, ", ".join(repr(p) for p in PRECISIONS)))
+    if backend == "torch" and precision != "fp32":
+        raise ValueError("%s: the torch backend computes in the network's own dtype: precision='fp32' only" % who)
+    return precision
+
+
+@contextlib.contextmanager
+def planned_precision(owner, precision):
+    """plan(..., precision=...): the owner's routes under `precision` while the plan is drawn up."""
+    kept = owner.precision
+    owner.precision = kept if precision is None else check_precision(type(owner).__name__, precision, "hip")
+    try:
+        yield
+    finally:
+        owner.precision = kept
+
+
+def split_workspace_bytes(B, C, H, W, K):
+    """ffwm_conv3x3_wg_split_workspace_bytes without the library (plan() touches no device; test_wino_split_cpu.py holds the two
+    together): V (a hi and a lo bf16 per entry, C rounded up to 32) and fp32 M, both padded to the 128 tile."""
+    T = (B * ((H + 1) // 2) * ((W + 1) // 2) + 127) // 128 * 128
+    return 16 * T * ((C + 31) // 32 * 32 + (K + 127) // 128 * 128) * 4
+
+
+def split_route_ok(L, x):
+    """The split route (csrc/conv_winograd_gemm_split.hip) serves a 3 x 3 / stride 1 / pad 1 layer with min(C, K) >= 32 whose
+    workspace fits SPLIT_WORKSPACE_LIMIT."""
+    K, C = L.w.shape[0], L.w.shape[1]
+    B, _, H, W = x.shape
+    return (L.k == 3 and L.stride == 1 and L.pad == 1 and min(C, K) >= 32
+            and split_workspace_bytes(B, C, H, W, K) <= SPLIT_WORKSPACE_LIMIT)
+
+
+def split_conv(owner, name, x, bias, epilogue, slope=0.2):
+    """Layer `name` of a folded network on the split route: its split weights are made at the first EAGER call (never inside a
+    capture: the rule conv.wg_entry states), the workspace is a slice of the owner's arena."""
+    from . import ops
+    L = owner.layers[name]
+    U = owner._split_u.get(name)
+    if U is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("%s: the split weights of %s would be made inside a graph capture; run one eager pass first" % (type(owner).__name__, name))
+        U = owner._split_u[name] = ops.conv3x3_wg_split_weights(L.w)
+    B, C, H, W = x.shape
+    K = L.w.shape[0]
+    ws = owner.arena.take(ops.conv3x3_wg_split_workspace_floats(B, C, H, W, K), x.device)
+    return ops.conv3x3_wg_split(x, U, bias, epilogue, slope=slope, K=K, workspace=ws)
+
+
+def conv_route(L, x, act, precision="fp32"):
     """Which kernel serves the convolution L (a layer tuple with w, k, stride, pad) on input x (a tensor or a _Spec): the predicates
-    of conv.py, no thresholds here.  Shared by FoldedFFWM and identity_eval.FoldedLightCNN."""
+    of conv.py, no thresholds here.  Shared by FoldedFFWM and identity_eval.FoldedLightCNN.  precision="bf16x3": "winograd_split"
+    wherever split_route_ok says so."""
     from . import conv
     K, C = L.w.shape[0], L.w.shape[1]
+    if precision == "bf16x3" and split_route_ok(L, x):
+        return "winograd_split"
     if L.k == 3 and L.stride == 1 and L.pad == 1 and min(C, K) >= 32 and conv.winograd_ok(x, L.w, act):
         return "winograd"                                   # conv.winograd_eligible + winograd_ok
     if (L.k in (3, 4) and L.stride in (1, 2) and L.pad < L.k and min(C, K) >= 32 and (L.stride == 2 or L.k == 3)
@@ -152,6 +217,10 @@ class _HipExec(_PlanExec):
         L = self.o.layers[name]
         route = self.o._route(name, x, act)
         self.launches.append((name, route))
+        if route == "winograd_split":
+            if L.b is None:
+                return split_conv(self.o, name, x, None, "none")
+            return split_conv(self.o, name, x, L.b, "lrelu" if act == LRELU else "bias", slope)
         if route == "winograd":
             return ops.conv3x3_winograd(x, L.w, L.b, act=act, slope=slope if act else 0.0, frozen=self.o._wino.setdefault(name, {}))
         if route == "conv_mfma":
@@ -263,11 +332,13 @@ class FoldedFFWM(object):
         rec32, rec64, rec128, att = folded(img, [flow32, flow64, flow128], return_att=True)
 
     backend: "hip" (float32 GPU network; the default on a GPU) or "torch" (a PyTorch composition of the same folded arithmetic, any
-    dtype and device).  graph=True (hip only) replays the forward from one captured hipGraph, re-captured when the input shape
+    dtype and device).  precision: "fp32" (the default) or, hip only, "bf16x3": the 3 x 3 / stride 1 layers that split_route_ok names
+    run their Winograd GEMMs on the bf16 MFMA with hi / lo split operands (csrc/conv_winograd_gemm_split.hip; float32 tensors in and
+    out, error bound and non-finite contract in include/ffwm_hip.h).  graph=True (hip only) replays the forward from one captured hipGraph, re-captured when the input shape
     changes: the OUTPUTS ARE STATIC BUFFERS THAT THE NEXT CALL OVERWRITES -- clone what must survive it.  return_features=True also
     returns {"e0".."e3", "d0".."d2", "dres0".."dres2"}, the outputs of those modules, and always runs un-captured."""
 
-    def __init__(self, net, graph=False, backend=None):
+    def __init__(self, net, graph=False, backend=None, precision="fp32"):
         from . import nets
         if not isinstance(net, nets.FFWM):
             raise TypeError("FoldedFFWM: a nets.FFWM is expected")
@@ -284,6 +355,8 @@ class FoldedFFWM(object):
             raise NotImplementedError("FoldedFFWM: the hip backend takes float32 GPU networks only (backend='torch' for the rest)")
         if graph and backend != "hip":
             raise ValueError("FoldedFFWM: graph replay needs the hip backend")
+        self.precision = check_precision("FoldedFFWM", precision, backend)
+        self._split_u = {}
         self.backend, self.use_graph = backend, bool(graph)
         self.device, self.dtype = p.device, p.dtype
         self.n_levels = net.layers
@@ -354,8 +427,11 @@ class FoldedFFWM(object):
 
     # ---- routes -------------------------------------------------------------------------------------------------------
     def _route(self, name, x, act):
-        """Which kernel serves convolution `name` on input x (a tensor or a _Spec): the predicates of conv.py, no thresholds here."""
-        return conv_route(self.layers[name], x, act)
+        """Which kernel serves convolution `name` on input x (a tensor or a _Spec): the predicates of conv.py, no thresholds here.
+        precision="bf16x3" sends what split_route_ok names to the split route, but for the layers of SPLIT_EXCLUDED_LAYERS."""
+        if act not in (LRELU, NONE) or name in SPLIT_EXCLUDED_LAYERS:
+            return conv_route(self.layers[name], x, act)
+        return conv_route(self.layers[name], x, act, self.precision)
 
     # ---- the forward, once for all executors ----------------------------------------------------------------------------
     def _res_block(self, ex, path, x, gate=None):
@@ -404,10 +480,12 @@ class FoldedFFWM(object):
             recons.append(ex.head("rec%d.0" % i, fdec))
         return tuple(recons[-3:]) + (att,)
 
-    def plan(self, B, H, W):
-        """The ordered launches of one forward at batch B and H x W images as [(layer name, kind)], kind in KINDS; no device is touched."""
+    def plan(self, B, H, W, precision=None):
+        """The ordered launches of one forward at batch B and H x W images as [(layer name, kind)], kind in KINDS; no device is touched.
+        precision: the plan the hip backend would follow under that precision (default: this object's own)."""
         ex = _PlanExec(self)
-        self._run(ex, _Spec(B, 3, H, W), [_Spec(B, 2, H >> (self.n_levels - 1 - i), W >> (self.n_levels - 1 - i)) for i in range(self.n_levels)], True)
+        with planned_precision(self, precision):
+            self._run(ex, _Spec(B, 3, H, W), [_Spec(B, 2, H >> (self.n_levels - 1 - i), W >> (self.n_levels - 1 - i)) for i in range(self.n_levels)], True)
         return ex.launches
 
     def _forward(self, x, flows, want_att=True, features=None, beside=None):
@@ -455,11 +533,11 @@ class Frontalizer(object):
     which needs no flow, on a side stream beside the flow net.  THE RESULT'S TENSORS ARE STATIC BUFFERS THAT THE NEXT CALL OVERWRITES.  The
     guided filter (it needs the ground truth) and the LightCNN feature are the caller's: INTEGRATION.md."""
 
-    def __init__(self, flowNetF, netG, graph=True, backend=None):
+    def __init__(self, flowNetF, netG, graph=True, backend=None, precision="fp32"):
         if flowNetF.training or netG.training:
             raise ValueError("Frontalizer snapshots eval-mode weights: call .eval() on both networks first")
-        self.netG = FoldedFFWM(netG, graph=False, backend=backend)
-        self.backend = self.netG.backend
+        self.netG = FoldedFFWM(netG, graph=False, backend=backend, precision=precision)          # the flow net stays fp32
+        self.backend, self.precision = self.netG.backend, self.netG.precision
         if graph and self.backend != "hip":
             raise ValueError("Frontalizer: graph replay needs the hip backend")
         self.use_graph = bool(graph)
@@ -474,7 +552,7 @@ class Frontalizer(object):
         self._graph = None
 
     @classmethod
-    def from_checkpoints(cls, load_dir, epoch="latest", ngf=64, device=None, graph=True, backend=None):
+    def from_checkpoints(cls, load_dir, epoch="latest", ngf=64, device=None, graph=True, backend=None, precision="fp32"):
         """Load `<epoch>_net_flowNetF.pth` and `<epoch>_net_netG.pth` as the reference's BaseModel.save_networks wrote them
         (models/base_model.py:172-229) into nets.FlowNet(ngf) / nets.FFWM(sn=True); no trainer is constructed."""
         from . import nets
@@ -486,11 +564,11 @@ class Frontalizer(object):
                 del sd._metadata
             mod.load_state_dict(sd)
             mod.to(device).eval()
-        return cls(mods["flowNetF"], mods["netG"], graph=graph, backend=backend)
+        return cls(mods["flowNetF"], mods["netG"], graph=graph, backend=backend, precision=precision)
 
-    def plan(self, B, H, W):
+    def plan(self, B, H, W, precision=None):
         """netG's launches (FoldedFFWM.plan); the flow net's and the image warp's are FoldedFlowNet's and one `warp` launch."""
-        return self.netG.plan(B, H, W)
+        return self.netG.plan(B, H, W, precision)
 
     def _forward(self, img):
         if self.backend == "torch":

@@ -23,10 +23,10 @@ import os
 import torch
 import torch.nn.functional as F
 
-from .ffwm_eval import Frontalizer, _Spec, conv_route, torch_warp
+from .ffwm_eval import Frontalizer, _Spec, check_precision, conv_route, planned_precision, split_conv, split_route_ok, torch_warp
 from .graphs import GraphedForward
 
-KINDS = ("winograd", "conv_mfma", "vendor_conv", "mfm_tail", "linear", "mfm")
+KINDS = ("winograd", "winograd_split", "conv_mfma", "vendor_conv", "mfm_tail", "linear", "mfm")
 
 # Layers that stay on the vendor's convolution although a hand-written kernel would serve them: those where the vendor's kernel measured
 # faster at BOTH batch 1 and batch 8 as device time inside a captured graph, which is where FaceIdentifier runs them
@@ -34,6 +34,13 @@ KINDS = ("winograd", "conv_mfma", "vendor_conv", "mfm_tail", "linear", "mfm")
 # 48 against 38-40) and the 128-channel layers at 16 x 16 (14.6 against 10.8 us, 30.4 against 27.5).
 VENDOR_LAYERS = frozenset(["block2.%d.conv%d" % (j, c) for j in range(2) for c in (1, 2)]
                           + ["block4.%d.conv%d" % (j, c) for j in range(4) for c in (1, 2)] + ["group4.conv"])
+
+# Layers that stay on their fp32 route under precision="bf16x3": those where the split route (csrc/conv_winograd_gemm_split.hip)
+# measured slower than the layer's present route at BOTH batch 1 and batch 8 by more than the larger min-max spread
+# (tools/split_conv_bench.py; the table is in profiles/wino_gemm_split.txt): the 48-channel layers at 64 x 64 -- 16.5 against 21.8 us
+# and 24.2 against 46.2 us (48 -> 96), 16.1 against 27.6 and 42.1 against 69.4 (48 -> 192).  C = 48 is padded to two 32-channel
+# stages, and at these planes the transforms around the GEMM move more bytes than the fused fp32 kernels.
+SPLIT_EXCLUDED_LAYERS = frozenset(["block1.0.conv1", "block1.0.conv2", "group1.conv"])
 
 _Layer = collections.namedtuple("_Layer", "w b k stride pad")
 _BLOCKS = (1, 2, 3, 4)          # residual blocks in front of group1 .. group4
@@ -93,6 +100,8 @@ def run_conv(owner, name, x, route):
     through this)."""
     from . import flownet_eval, ops
     L = owner.layers[name]
+    if route == "winograd_split":
+        return split_conv(owner, name, x, None, "none")
     if route == "winograd":
         return ops.conv3x3_winograd(x, L.w, None, act=0, frozen=owner._wino.setdefault(name, {}))
     if route == "conv_mfma":
@@ -147,10 +156,11 @@ class FoldedLightCNN(object):
         fc, pool = net(gray)            # [B, 256], [B, 128, 8, 8] for 128 x 128 inputs
 
     backend: "hip" (float32 GPU network; the default on a GPU) or "torch" (the same arithmetic as a PyTorch composition, any dtype
-    and device).  graph=True (hip only) replays the forward from one captured hipGraph, re-captured when the input shape changes:
+    and device).  precision: "fp32" (the default) or, hip only, "bf16x3": the 3 x 3 / stride 1 layers that ffwm_eval.split_route_ok
+    names run on csrc/conv_winograd_gemm_split.hip (bf16 MFMA, hi / lo split operands; float32 tensors in and out).  graph=True (hip only) replays the forward from one captured hipGraph, re-captured when the input shape changes:
     THE OUTPUTS ARE STATIC BUFFERS THAT THE NEXT CALL OVERWRITES -- clone what must survive it.  `fc2` is neither kept nor run."""
 
-    def __init__(self, net, graph=False, backend=None):
+    def __init__(self, net, graph=False, backend=None, precision="fp32"):
         from . import nets
         if not isinstance(net, nets.LightCNN29):
             raise TypeError("FoldedLightCNN: a nets.LightCNN29 is expected")
@@ -165,6 +175,8 @@ class FoldedLightCNN(object):
             raise NotImplementedError("FoldedLightCNN: the hip backend takes float32 GPU networks only (backend='torch' for the rest)")
         if graph and backend != "hip":
             raise ValueError("FoldedLightCNN: graph replay needs the hip backend")
+        self.precision = check_precision("FoldedLightCNN", precision, backend)
+        self._split_u = {}
         self.backend, self.use_graph = backend, bool(graph)
         self.device, self.dtype = p.device, p.dtype
         self.layers = collections.OrderedDict()
@@ -193,7 +205,10 @@ class FoldedLightCNN(object):
 
     def _route(self, name, x):
         """Which kernel serves convolution `name` on input x (a tensor or a _Spec): ffwm_eval.conv_route, FoldedFFWM's predicates,
-        with no activation; a layer of VENDOR_LAYERS stays on the vendor's kernel."""
+        with no activation; a layer of VENDOR_LAYERS stays on the vendor's kernel.  precision="bf16x3": the split route wherever
+        ffwm_eval.split_route_ok says so (VENDOR_LAYERS included), but for the layers of SPLIT_EXCLUDED_LAYERS."""
+        if self.precision == "bf16x3" and name not in SPLIT_EXCLUDED_LAYERS and split_route_ok(self.layers[name], x):
+            return "winograd_split"
         if name in VENDOR_LAYERS:
             return "vendor_conv"
         return conv_route(self.layers[name], x, 0)
@@ -208,10 +223,12 @@ class FoldedLightCNN(object):
             x = ex.layer("group%d.conv" % i, x, pool=_POOL_BEHIND["group%d.conv" % i])
         return ex.fc(x), x
 
-    def plan(self, B, H, W):
-        """The ordered launches of one forward at batch B and H x W inputs as [(layer name, kind)], kind in KINDS; no device is touched."""
+    def plan(self, B, H, W, precision=None):
+        """The ordered launches of one forward at batch B and H x W inputs as [(layer name, kind)], kind in KINDS; no device is touched.
+        precision: the plan the hip backend would follow under that precision (default: this object's own)."""
         ex = _PlanExec(self)
-        self._run(ex, _Spec(B, 1, H, W))
+        with planned_precision(self, precision):
+            self._run(ex, _Spec(B, 1, H, W))
         return ex.launches
 
     def _forward(self, x):
@@ -264,12 +281,13 @@ class FaceIdentifier(object):
     input shape or the gallery size changes: THE RESULT'S TENSORS ARE STATIC BUFFERS THAT THE NEXT CALL OVERWRITES -- clone what must
     survive it."""
 
-    def __init__(self, flowNetF, netG, lightcnn, crop=False, graph=True, topk=1, backend=None):
-        self.front = Frontalizer(flowNetF, netG, graph=False, backend=backend)
+    def __init__(self, flowNetF, netG, lightcnn, crop=False, graph=True, topk=1, backend=None, precision="fp32"):
+        self.front = Frontalizer(flowNetF, netG, graph=False, backend=backend, precision=precision)
         self.backend = self.front.backend
         if graph and self.backend != "hip":
             raise ValueError("FaceIdentifier: graph replay needs the hip backend")
-        self.net = FoldedLightCNN(lightcnn, graph=False, backend=self.backend)
+        self.net = FoldedLightCNN(lightcnn, graph=False, backend=self.backend, precision=precision)
+        self.precision = self.net.precision
         self.crop, self.use_graph, self.topk = bool(crop), bool(graph), int(topk)
         self.gallery_keys, self.gallery_features = None, None
         self._graph = None
@@ -278,7 +296,8 @@ class FaceIdentifier(object):
             self._eager_arena = Arena()          # feature()'s: see there
 
     @classmethod
-    def from_checkpoints(cls, load_dir, epoch, lightcnn_path, ngf=64, crop=False, device=None, graph=True, backend=None, topk=1):
+    def from_checkpoints(cls, load_dir, epoch, lightcnn_path, ngf=64, crop=False, device=None, graph=True, backend=None, topk=1,
+                         precision="fp32"):
         """Frontalizer.from_checkpoints' two files, and `lightcnn_path`: a plain LightCNN-29 state dict as FFWMModel.load_network reads
         it (models/ffwm_model.py:212-215)."""
         from . import nets
@@ -293,11 +312,11 @@ class FaceIdentifier(object):
         light = nets.LightCNN29()
         light.load_state_dict(torch.load(lightcnn_path, map_location="cpu"))
         light.to(device).eval()
-        return cls(mods["flowNetF"], mods["netG"], light, crop=crop, graph=graph, topk=topk, backend=backend)
+        return cls(mods["flowNetF"], mods["netG"], light, crop=crop, graph=graph, topk=topk, backend=backend, precision=precision)
 
-    def plan(self, B, H=128, W=128):
+    def plan(self, B, H=128, W=128, precision=None):
         """The LightCNN's launches (FoldedLightCNN.plan); the frontaliser's are Frontalizer.plan's, plus one input and the matcher's."""
-        return self.net.plan(B, H, W)
+        return self.net.plan(B, H, W, precision)
 
     def _input(self, img):
         if self.backend == "torch":

@@ -924,6 +924,74 @@ def conv3x3_wg_tile(B, C, H, W, K):
     return int(_lib.load().ffwm_conv3x3_wg_tile(int(B), int(C), int(H), int(W), int(K)))
 
 
+# ---------------------------------------------------------------- the same route on the bf16 MFMA (csrc/conv_winograd_gemm_split.hip)
+WG_SPLIT_EPILOGUES = {"none": 0, "bias": 1, "lrelu": 2}
+
+
+def conv3x3_wg_split_weights(weight):
+    """U = G w G^T of a FROZEN Conv2d(C, K, 3, 1, 1) weight [K, C, 3, 3], every entry split in two bf16 terms, for conv3x3_wg_split.
+    One launch; made once per layer.  A float32 tensor that holds the bf16 halves (ffwm_conv3x3_wg_split_weights_bytes)."""
+    if not (weight.is_cuda and weight.dtype == torch.float32 and weight.is_contiguous() and weight.dim() == 4 and tuple(weight.shape[2:]) == (3, 3)):
+        raise ValueError("conv3x3_wg_split_weights: a contiguous float32 [K, C, 3, 3] weight on the GPU")
+    K, C = weight.shape[0], weight.shape[1]
+    lib = _lib.load()
+    U = weight.new_empty((lib.ffwm_conv3x3_wg_split_weights_bytes(K, C) // 4,))
+    with _on_device(weight) as stream:
+        _lib.check(lib.ffwm_conv3x3_wg_split_weights(_ptr(weight), _ptr(U), K, C, _lib.F32, stream), "ffwm_conv3x3_wg_split_weights")
+    return U
+
+
+def conv3x3_wg_split(x, U, bias, epilogue, slope=0.2, out=None, K=None, tile=0, workspace=None):
+    """Conv2d(C, K, 3, 1, 1) of float32 x [B, C, H, W] with the split transformed weights U of conv3x3_wg_split_weights: input
+    transform + split, 16 GEMMs on the bf16 MFMA (lo hi + hi lo + hi hi per product), output transform.  epilogue: "none", "bias" or
+    "lrelu" (bias + LeakyReLU(slope)).  K: the output channels (default: bias.numel()).  tile (tests): 64 / 128 fixes the GEMM tile.
+    workspace: a float32 tensor of at least ffwm_conv3x3_wg_split_workspace_bytes (an arena slice), else allocated.  Error bound and
+    the non-finite contract: include/ffwm_hip.h."""
+    _check("conv3x3_wg_split", x, out)
+    for t in (U, bias, workspace):
+        if t is not None and (t.device != x.device or t.dtype != x.dtype or not t.is_contiguous()):
+            raise ValueError("conv3x3_wg_split: U, bias and workspace must be contiguous tensors of the input's device and dtype")
+    if x.dtype != torch.float32:
+        raise TypeError("conv3x3_wg_split: float32 only")
+    B, C, H, W = x.shape
+    if K is None:
+        if bias is None:
+            raise ValueError("conv3x3_wg_split: K is needed when there is no bias")
+        K = bias.numel()
+    lib = _lib.load()
+    if U.numel() * 4 != lib.ffwm_conv3x3_wg_split_weights_bytes(K, C):
+        raise ValueError("conv3x3_wg_split: U does not belong to a layer with %d input and %d output channels" % (C, K))
+    epi = WG_SPLIT_EPILOGUES[epilogue]
+    if epi and bias is None:
+        raise ValueError("conv3x3_wg_split: the %s epilogue needs a bias" % epilogue)
+    if bias is not None and bias.numel() != K:
+        raise ValueError("conv3x3_wg_split: bias must be a contiguous vector of %d elements" % K)
+    shape = (B, K, H, W)
+    if out is None:
+        out = x.new_empty(shape)
+    elif tuple(out.shape) != shape:
+        raise ValueError("conv3x3_wg_split: out has the wrong shape")
+    need = lib.ffwm_conv3x3_wg_split_workspace_bytes(B, C, H, W, K) // 4
+    if workspace is None:
+        workspace = x.new_empty((need,))
+    elif workspace.numel() < need:
+        raise ValueError("conv3x3_wg_split: the workspace is too small")
+    with _on_device(x) as stream:
+        _lib.check(lib.ffwm_conv3x3_wg_split_forward(_ptr(x), _ptr(U), _ptr(bias), _ptr(out), _ptr(workspace), B, C, H, W, K, epi,
+                                                     float(slope), int(tile), _dtype_code(x), stream), "ffwm_conv3x3_wg_split_forward")
+    return out
+
+
+def conv3x3_wg_split_tile(B, C, H, W, K):
+    """The GEMM tile (64 or 128) the plan of conv3x3_wg_split takes for this call on the current device."""
+    return int(_lib.load().ffwm_conv3x3_wg_split_tile(int(B), int(C), int(H), int(W), int(K)))
+
+
+def conv3x3_wg_split_workspace_floats(B, C, H, W, K):
+    """The workspace of conv3x3_wg_split in float32 elements (ffwm_conv3x3_wg_split_workspace_bytes / 4); no device is touched."""
+    return int(_lib.load().ffwm_conv3x3_wg_split_workspace_bytes(int(B), int(C), int(H), int(W), int(K))) // 4
+
+
 # ---------------------------------------------------------------- LightCNN max-feature-map
 def _mfm_dims(x):
     if x.dim() < 2 or x.shape[1] % 2:

@@ -609,6 +609,33 @@ int ffwm_conv3x3_wg_forward_tiled(const void* input, const void* U, const void* 
                                   int64_t B, int64_t C, int64_t H, int64_t W, int64_t K, int epilogue, const void* relu_mask,
                                   int tile, int dtype, void* stream);
 
+/* The forward of the same three-launch route with its 16 GEMMs on the bf16 matrix instruction (csrc/conv_winograd_gemm_split.hip):
+ * float32 tensors in and out; U = G w G^T and V = B^T d B are computed in fp32 as above, every entry x is then split in two bf16
+ * terms, hi = bf16_rn(x), lo = bf16_rn(x - hi), and a product sum is taken as sum_c (U_lo V_hi + U_hi V_lo + U_hi V_hi) in one fp32
+ * accumulator (v_mfma_f32_32x32x16_bf16, three per 16 channels).  No atomics, no split of the reduction: deterministic.  Forward
+ * only, no ReLU mask, no max-feature-map.
+ *   Error per output element against the float64 convolution of the given tensors, u = 2^-24, MAG = 1 + 2^-6, mag_patch = sum_c (max
+ *   |x_c| over the 4 x 4 patch of the element's 2 x 2 tile) (sum of |w_kc| over the 9 taps) + |bias_k|:
+ *       |y - ref| <= 16 (2^-16 MAG + 4 (3 C + 11) u MAG) mag_patch + (4 + post) u |ref| + eta
+ *   (post = 1 behind LeakyReLU; eta ~ 1e-36 covers bf16 terms, products and partial sums below 2^-126 that may be flushed to zero;
+ *   derivation: tests/wino_split_cases.py).  At C = 64 that is 1.0e-3 mag_patch against 2.9e-4 of the fp32 route's bound.
+ *   Non-finite contract: a NaN in the input makes the outputs inside the reach of its 4 x 4 patches NaN, a NaN in a weight its output
+ *   channel.  An INFINITE entry of U or V has hi = inf and lo = bf16(inf - inf) = NaN, so an infinity in the input or a weight
+ *   behaves as such a NaN.  Finite |x| >= 2^125 is outside the contract: V sums four inputs, and hi may round to infinity.
+ *   ffwm_conv3x3_wg_split_weights: weight [K, C, 3, 3] -> the split U, ffwm_conv3x3_wg_split_weights_bytes(K, C) bytes, 16-byte
+ *     aligned, stored [16][Cp / 8][hi, lo][K][8] bf16 (Cp = C rounded up to 32, channels past C zero).  Made once per layer.
+ *   ffwm_conv3x3_wg_split_forward: input [B, C, H, W] -> output [B, K, H, W].  bias [K] (NULL with FFWM_WGS_NONE).  workspace:
+ *     ffwm_conv3x3_wg_split_workspace_bytes(B, C, H, W, K) bytes (enough for either tile), 16-byte aligned, rewritten by every call.
+ *     tile: 64 or 128 fixes the GEMM tile, 0 takes the plan's (ffwm_conv3x3_wg_split_tile: the rule of ffwm_conv3x3_wg_tile). */
+enum { FFWM_WGS_NONE = 0, FFWM_WGS_BIAS = 1, FFWM_WGS_BIAS_LRELU = 2 };
+int64_t ffwm_conv3x3_wg_split_weights_bytes(int64_t K, int64_t C);
+int64_t ffwm_conv3x3_wg_split_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W, int64_t K);
+int ffwm_conv3x3_wg_split_weights(const void* weight, void* U, int64_t K, int64_t C, int dtype, void* stream);
+int ffwm_conv3x3_wg_split_tile(int64_t B, int64_t C, int64_t H, int64_t W, int64_t K);
+int ffwm_conv3x3_wg_split_forward(const void* input, const void* U, const void* bias, void* output, void* workspace,
+                                  int64_t B, int64_t C, int64_t H, int64_t W, int64_t K, int epilogue, double negative_slope,
+                                  int tile, int dtype, void* stream);
+
 /* One Adam step (no weight decay, no amsgrad: torch.optim.Adam as models/ffwm_model.py:46-49 and
  * models/flownet_model.py:33 construct it) over FLAT float32 arrays of n elements, 16-byte aligned: parameters,
  * gradients, first and second moments.  `step` is the 1-based step count (bias corrections 1 - beta^step). */
