@@ -92,6 +92,8 @@ _SIGNATURES = {
     "ffwm_conv3x3_wg_split_weights": [_p, _p, _i64, _i64, _i, _p],
     "ffwm_conv3x3_wg_split_forward": [_p, _p, _p, _p, _p] + [_i64] * 5 + [_i, ctypes.c_double, _i, _i, _p],
     "ffwm_conv3x3_wg_split_tile": [_i64] * 5,
+    "ffwm_conv3x3_wg_split_weights_dgrad": [_p, _p, _i64, _i64, _i, _p],
+    "ffwm_conv3x3_wg_split_apply": [_p, _p, _p, _p, _p] + [_i64] * 5 + [_i, _p, _i, _i, _p],
     "ffwm_mfm_tail_forward": [_p, _p, _p, _p] + [_i64] * 4 + [_i, _i, _p],
     "ffwm_identity_input": [_p, _p] + [_i64] * 4 + [_i, _i, _p],
     "ffwm_identity_input_backward": [_p, _p] + [_i64] * 4 + [_i, _i, _p],

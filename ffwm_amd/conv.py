@@ -438,8 +438,58 @@ WG_TABLE = {
 }
 
 
+# The same classes under loss_precision="bf16x3" (wg_set_precision): (C, K) -> the T ranges in which the call runs its 16 GEMMs on the
+# bf16 MFMA with hi / lo split operands (csrc/conv_winograd_gemm_split.hip) instead of the route it has under "fp32" -- WG_TABLE's
+# fp32 GEMMs, or the vendor.  Consulted ONLY under "bf16x3"; a layer, direction or T outside it keeps exactly the route it has today.
+# From tools/split_loss_bench.py, part "layers" (profiles/wino_split_train.txt): every distinct frozen 3x3 shape of the train step at
+# batch 8, both directions, the data gradient under a ReLU mask where the network has one, 20 calls per captured graph, median of 7
+# replays, five alternating pairs; a (class, direction, T) is listed only where the split route's median is below its parent
+# route's by more than the larger min-max spread of the two.  The ends of a range are measured shapes; between two winners of one
+# class the route is taken too.  512 -> 512 at T = 40 (VGG19 conv5_1 on the crops) is a forward WG_TABLE leaves to the vendor: 30.5
+# -> 27.5 us.  What keeps its route: the 64- and 128-output-channel layers (the vendor's 22-35 us stand), T = 32, the masked data
+# gradients of 256 -> 256 at T = 512 / 640 (37.5 -> 40.7, 41.4 -> 43.4 us) and of 256 -> 512 below T = 512.  One CHOICE beyond the
+# rule: 128 -> 256 is shared by both networks and kept uniform, as in WG_TABLE: its forward wins at T = 2048 alone (45.4 -> 36.9;
+# at T = 512 / 640 the difference is inside the spread under VGG19 and wins only under LightCNN's autograd call, 27.9 -> 26.9), its
+# data gradient wins under LightCNN at T = 512 (29.0 -> 26.9) and loses under VGG19's mask at every T, so it stays where it is.
+WGS_TABLE = {
+    (128, 256): ((2048, 2048), _WG_NEVER),         # VGG conv3_1 on the 128 px image
+    (256, 256): ((512, 2048), (2048, 2048)),       # VGG conv3_2-4
+    (256, 512): ((160, 512), (512, 512)),          # VGG conv4_1
+    (512, 512): ((40, 512), (128, 512)),           # VGG conv4_2-4, conv5_1
+    (96, 192): ((2048, 2048), (2048, 2048)),       # LightCNN block2
+    (96, 384): ((2048, 2048), (2048, 2048)),       # LightCNN group2
+    (192, 384): ((512, 512), (512, 512)),          # LightCNN block3
+    (192, 256): ((512, 512), (512, 512)),          # LightCNN group3
+}
+PRECISIONS = ("fp32", "bf16x3")
+
+
+def wg_set_precision(net, precision):
+    """Stamp the arithmetic of the batched-GEMM Winograd route on every nn.Conv2d of the frozen network `net`: "fp32" (what an
+    unstamped layer has) or "bf16x3" (WGS_TABLE is consulted first).  Per layer, not per process: two trainers may differ.  An entry
+    of wg_entry made under the other precision is stale; wg_prepare(net) makes the new one.  -> layers stamped."""
+    if precision not in PRECISIONS:
+        raise ValueError("wg_set_precision: precision must be one of %s, got %r" % (PRECISIONS, precision))
+    n = 0
+    for m in net.modules():
+        if isinstance(m, nn.Conv2d):
+            m.__dict__["_wg_precision"] = precision
+            n += 1
+    return n
+
+
+def _wg_precision(layer):
+    return "fp32" if layer is None else layer.__dict__.get("_wg_precision", "fp32")
+
+
 def _wg_class(weight):
     return WG_TABLE.get((weight.shape[1], weight.shape[0]), (_WG_NEVER, _WG_NEVER))
+
+
+def _wgs_class(weight, precision):
+    if precision != "bf16x3":
+        return (_WG_NEVER, _WG_NEVER)
+    return WGS_TABLE.get((weight.shape[1], weight.shape[0]), (_WG_NEVER, _WG_NEVER))
 
 
 def _wg_in(t, rng):
@@ -450,64 +500,109 @@ def _wg_tiles(x):
     return x.shape[0] * ((x.shape[2] + 1) // 2) * ((x.shape[3] + 1) // 2)
 
 
+def _wg_inside(inner, outer):
+    """Whether every T of the range `inner` lies in `outer` (an empty range lies in every range)."""
+    return inner[0] > inner[1] or (outer[0] <= inner[0] and inner[1] <= outer[1])
+
+
+def wg_route(t, weight, precision, direction):
+    """The route of a call with t tiles through a frozen layer, direction 0 (forward) or 1 (data gradient): "split" (WGS_TABLE, under
+    "bf16x3" only), "fp32" (WG_TABLE) or None (the forward: the layer is not on this route at all; the data gradient: the vendor's)."""
+    if _wg_in(t, _wgs_class(weight, precision)[direction]):
+        return "split"
+    if _wg_in(t, _wg_class(weight)[direction]):
+        return "fp32"
+    return None
+
+
 def wg_entry(layer, weight, create=True):
     """The transformed weights of a FROZEN layer, {0: U of the forward, 1: U of the data gradient -- only where WG_TABLE routes
-    the class's data gradient at all}, or None.  They live in the layer's __dict__ (they die with it), keyed by the weight's
-    version counter and address; they are built eagerly on the first call -- or by wg_prepare() when the trainer is built and
+    the class's data gradient at all}, or None.  Under wg_set_precision(net, "bf16x3") also {"s0", "s1": the split U of the forward /
+    the data gradient} for the directions WGS_TABLE names, and no fp32 U for a direction whose whole WG_TABLE range goes to the split
+    route.  They live in the layer's __dict__ (they die with it), keyed by the weight's
+    version counter and address (and the precision, when it is not "fp32"); they are built eagerly on the first call -- or by
+    wg_prepare() when the trainer is built and
     again when it captures -- and the building stream is synchronised, since the loss networks' passes run on side streams.  A
     call made while a stream is capturing may READ a valid entry but never creates one: a transform that was only captured, not
     run, must not be recorded as valid.  So weights loaded AFTER the entries were made (load_state_dict bumps the version
     counter) are transformed again by the next eager call -- FFWMTrainer.capture() runs wg_prepare and its eager warm-up steps
     first -- and a layer whose entry is stale inside a capture silently takes the vendor route for that graph, as frozen_cache's
-    layers re-transform per call.  Only a frozen nn.Parameter qualifies (see frozen_cache).  16 K (C rounded up to 16) floats
-    per direction: 0.25 GiB for the routed classes of VGG19 (170 MiB) and LightCNN-29 (87 MiB) together (wg_prepare returns
-    the bytes)."""
+    layers re-transform per call.  Only a frozen nn.Parameter qualifies (see frozen_cache).  16 K (C rounded up to 16; split: to
+    32) floats per direction: 0.25 GiB for the routed classes of VGG19 (170 MiB) and LightCNN-29 (87 MiB) together (wg_prepare
+    returns the bytes)."""
     if (not isinstance(weight, nn.Parameter)) or weight.requires_grad or hasattr(layer, "weight_orig") or getattr(weight, "_ffwm_flat_adam", False):
         return None
-    key = (weight._version, weight.data_ptr())
+    precision = _wg_precision(layer)
+    key = (weight._version, weight.data_ptr()) + (() if precision == "fp32" else (precision,))
     d = layer.__dict__.get("_wg_frozen")
     if d is not None and d.get("key") == key:
         return d
     if not create or torch.cuda.is_current_stream_capturing():
         return None
     w = weight.detach().contiguous()
-    d = {"key": key, 0: ops.conv3x3_wg_weights(w, False)}
-    if _wg_class(weight)[1] != _WG_NEVER:
-        d[1] = ops.conv3x3_wg_weights(w, True)
+    wg, wgs = _wg_class(weight), _wgs_class(weight, precision)
+    d = {"key": key}
+    for direction in (0, 1):
+        # the forward's fp32 U is made for every layer that reaches this function under "fp32" (as it always was)
+        if (direction == 0 and precision == "fp32") or not _wg_inside(wg[direction], wgs[direction]):
+            d[direction] = ops.conv3x3_wg_weights(w, bool(direction))
+        if wgs[direction] != _WG_NEVER:
+            d["s%d" % direction] = ops.conv3x3_wg_split_weights(w, data_gradient=bool(direction))
     torch.cuda.current_stream(weight.device).synchronize()
     layer.__dict__["_wg_frozen"] = d
     return d
 
 
+def _wg_entry_route(entry, t, weight, direction):
+    """wg_route of the precision the entry was made under, and None where the entry does not hold that route's weights."""
+    route = wg_route(t, weight, entry["key"][2] if len(entry["key"]) > 2 else "fp32", direction)
+    if route is not None and ("s%d" % direction if route == "split" else direction) not in entry:
+        return None
+    return route
+
+
 def wg_ok(x, weight, layer=None):
     """Whether the frozen Conv2d(C, K, 3, 1, 1) `layer` runs x on the batched-GEMM Winograd route: fp32, no autocast, a frozen
-    nn.Parameter, and (T, C, K) inside WG_TABLE.  With `layer`, also that its transformed weights exist or may be made now."""
+    nn.Parameter, and (T, C, K) inside WG_TABLE -- or, for a layer stamped "bf16x3", inside WGS_TABLE.  With `layer`, also that its
+    transformed weights exist or may be made now."""
     if not (_WG and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and weight.dtype == torch.float32
             and isinstance(weight, nn.Parameter) and not weight.requires_grad and not torch.is_autocast_enabled()
             and tuple(weight.shape[2:]) == (3, 3) and weight.shape[1] == x.shape[1]):
         return False
-    if not _wg_in(_wg_tiles(x), _wg_class(weight)[0]):
+    t = _wg_tiles(x)
+    if wg_route(t, weight, _wg_precision(layer), 0) is None:
         return False
     if layer is None:
         return True
     if not (layer.stride == (1, 1) and layer.padding == (1, 1) and layer.dilation == (1, 1) and layer.groups == 1
             and layer.padding_mode == "zeros"):
         return False
-    return wg_entry(layer, weight) is not None
+    entry = wg_entry(layer, weight)
+    return entry is not None and _wg_entry_route(entry, t, weight, 0) is not None
+
+
+def _wg_call(route, x, entry, direction, bias, epilogue, relu_mask=None, K=None):
+    """One call of the route `route` ("fp32" / "split") with the entry's U of that route and direction."""
+    if route == "split":
+        return ops.conv3x3_wg_split_frozen(x, entry["s%d" % direction], bias, epilogue, relu_mask=relu_mask, K=K)
+    return ops.conv3x3_wg(x, entry[direction], bias, epilogue, relu_mask=relu_mask, K=K)
 
 
 class _WgConv3x3(Function):
-    """A FROZEN Conv2d(C, K, 3, 1, 1) on csrc/conv_winograd_gemm.hip: relu(conv + bias) (relu=True; backward: the mask from the
+    """A FROZEN Conv2d(C, K, 3, 1, 1) on csrc/conv_winograd_gemm.hip or, where the layer is stamped "bf16x3" and WGS_TABLE names the
+    call, csrc/conv_winograd_gemm_split.hip: relu(conv + bias) (relu=True; backward: the mask from the
     saved output inside the input transform of the data gradient) or the bare convolution (LightCNN: bias + max-feature-map
-    follow as csrc/mfm.hip's kernels, whose backward needs both halves).  A data gradient outside WG_TABLE is the vendor's."""
+    follow as csrc/mfm.hip's kernels, whose backward needs both halves).  Each direction has its own route; a data gradient outside
+    both tables is the vendor's."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, entry, relu):
         x = x.contiguous()
         K, C = weight.shape[0], weight.shape[1]
-        y = ops.conv3x3_wg(x, entry[0], bias if relu else None, "relu" if relu else "none", K=K)
-        ctx.own_dgrad = 1 in entry and _wg_in(_wg_tiles(x), _wg_class(weight)[1])
-        ctx.save_for_backward(weight, y if relu else None, None if ctx.own_dgrad else x)
+        t = _wg_tiles(x)
+        y = _wg_call(_wg_entry_route(entry, t, weight, 0), x, entry, 0, bias if relu else None, "relu" if relu else "none", K=K)
+        ctx.dgrad_route = _wg_entry_route(entry, t, weight, 1)
+        ctx.save_for_backward(weight, y if relu else None, None if ctx.dgrad_route else x)
         ctx.entry, ctx.relu, ctx.C = entry, relu, C
         return y
 
@@ -516,8 +611,8 @@ class _WgConv3x3(Function):
     def backward(ctx, grad_y):
         weight, y, x = ctx.saved_tensors
         go = grad_y.contiguous()
-        if ctx.own_dgrad:
-            return ops.conv3x3_wg(go, ctx.entry[1], None, "none", relu_mask=y, K=ctx.C), None, None, None, None
+        if ctx.dgrad_route:
+            return _wg_call(ctx.dgrad_route, go, ctx.entry, 1, None, "none", relu_mask=y, K=ctx.C), None, None, None, None
         if ctx.relu:
             go = torch.ops.aten.threshold_backward(go, y, 0)
         gx = torch.ops.aten.convolution_backward(go, x, weight, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1, [True, False, False])[0]
@@ -529,7 +624,8 @@ def wg_bias_relu(x, layer):
     entry = wg_entry(layer, layer.weight)
     if torch.is_grad_enabled() and x.requires_grad:
         return _WgConv3x3.apply(x, layer.weight, layer.bias, entry, True)
-    return ops.conv3x3_wg(x.contiguous(), entry[0], layer.bias, "relu")
+    x = x.contiguous()
+    return _wg_call(_wg_entry_route(entry, _wg_tiles(x), layer.weight, 0), x, entry, 0, layer.bias, "relu")
 
 
 def wg_conv(x, layer):
@@ -537,17 +633,20 @@ def wg_conv(x, layer):
     entry = wg_entry(layer, layer.weight)
     if torch.is_grad_enabled() and x.requires_grad:
         return _WgConv3x3.apply(x, layer.weight, None, entry, False)
-    return ops.conv3x3_wg(x.contiguous(), entry[0], None, "none", K=layer.weight.shape[0])
+    x = x.contiguous()
+    return _wg_call(_wg_entry_route(entry, _wg_tiles(x), layer.weight, 0), x, entry, 0, None, "none", K=layer.weight.shape[0])
 
 
 def wg_bias_mfm(x, layer):
     """max-feature-map(layer(x)) of a frozen layer where no gradient is asked for: one epilogue, the pre-activation is never stored."""
     entry = wg_entry(layer, layer.weight)
-    return ops.conv3x3_wg(x.contiguous(), entry[0], layer.bias, "mfm", K=layer.weight.shape[0])
+    x = x.contiguous()
+    return _wg_call(_wg_entry_route(entry, _wg_tiles(x), layer.weight, 0), x, entry, 0, layer.bias, "mfm", K=layer.weight.shape[0])
 
 
 def wg_prepare(net):
-    """Build the transformed weights of every layer of the frozen network `net` whose class WG_TABLE routes, now: the forward's,
+    """Build the transformed weights of every layer of the frozen network `net` whose class WG_TABLE routes -- or, for layers stamped
+    "bf16x3", WGS_TABLE -- now: the forward's,
     and the data gradient's where the class's data gradient is routed (FFWMTrainer.__init__ and capture(): nothing is left to
     create when the step is captured).  Layers with a valid entry cost nothing.  -> bytes held."""
     n = 0
@@ -555,7 +654,8 @@ def wg_prepare(net):
         return n
     for m in net.modules():
         if (isinstance(m, nn.Conv2d) and m.kernel_size == (3, 3) and m.stride == (1, 1) and m.padding == (1, 1) and m.dilation == (1, 1)
-                and m.groups == 1 and m.weight.is_cuda and m.weight.dtype == torch.float32 and _wg_class(m.weight)[0] != _WG_NEVER):
+                and m.groups == 1 and m.weight.is_cuda and m.weight.dtype == torch.float32
+                and (_wg_class(m.weight)[0] != _WG_NEVER or _wgs_class(m.weight, _wg_precision(m))[0] != _WG_NEVER)):
             d = wg_entry(m, m.weight)
             if d is not None:
                 n += 4 * sum(u.numel() for k, u in d.items() if k != "key")

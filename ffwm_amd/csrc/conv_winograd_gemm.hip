@@ -26,10 +26,6 @@ namespace {
 enum { kWgNone = FFWM_WG_NONE, kWgBias = FFWM_WG_BIAS, kWgBiasRelu = FFWM_WG_BIAS_RELU, kWgBiasMfm = FFWM_WG_BIAS_MFM };
 constexpr int kWgStage = 16;             // input channels per LDS stage of the GEMM: four groups of four
 
-// ATen's NaN rule, as csrc/mfm.hip has it: maximum(a, b) is NaN when either operand is, relu(NaN) is NaN
-__device__ __forceinline__ float wg_max_nan(float a, float b) { return __builtin_isunordered(a, b) ? a + b : fmaxf(a, b); }
-__device__ __forceinline__ float wg_relu_nan(float v) { return v != v ? v : fmaxf(v, 0.f); }
-
 // ---------------------------------------------------------------------------------------------------- weights
 // U[p][c / 4][k][c % 4] = (G w Gt)[p] of output channel k and input channel c; zero for C <= c < Cp.  mode 0: w is [K][C][3][3];
 // mode 1 (data gradient): w is the layer's own [C][K][3][3], read transposed and rotated by 180 degrees.

@@ -18,6 +18,10 @@ struct WgGeo {
     int Tp, Kp;              // T and K rounded up to the GEMM tile
 };
 
+// ATen's NaN rule, as csrc/mfm.hip has it: maximum(a, b) is NaN when either operand is, relu(NaN) is NaN
+__device__ __forceinline__ float wg_max_nan(float a, float b) { return __builtin_isunordered(a, b) ? a + b : fmaxf(a, b); }
+__device__ __forceinline__ float wg_relu_nan(float v) { return v != v ? v : fmaxf(v, 0.f); }
+
 // y = At (M A) of one tile and output channel, + bv: M points at position 0, the positions are pstride floats apart
 __device__ __forceinline__ void wg_tile_of(const float* __restrict__ M, size_t pstride, float bv, float (&y)[4]) {
     float z[4][2];

@@ -9,6 +9,11 @@
 //   wgs_batched_gemm     M_p [Kp x Tp] = U_p [K x Cp] V_p [Cp x Tp]           p = 0 .. 15, fp32 M
 //   wgs_output_transform M [16][Kp][Tp]  ->  y [B, K, H, W]                   y = At M A (wg_tile_of), then bias / bias + LeakyReLU
 //
+// The frozen loss networks of the train step take the same GEMM through ffwm_conv3x3_wg_split_apply (loss_precision="bf16x3"): the
+// data gradient reads U made from the layer's own weight transposed and rotated (wgs_weights, mode 1) and the ReLU mask inside the
+// input transform, exactly as conv_winograd_gemm.hip does it; the output transform has that route's epilogues (bias, bias + ReLU,
+// bias + max-feature-map).  Bounds of those: tests/wino_split_train_cases.py.
+//
 // Layout.  Eight consecutive channels of one row (output channel k, or tile t) are one 16-byte line, the operand of one lane of the
 // MFMA (lane & 31 = row, lane >> 5 selects k 0-7 / 8-15); index [2] is the hi line, then the lo line.  hi and lo together take the 4
 // bytes per entry fp32 takes.  Cp = C rounded up to 32 (one LDS stage), zero filled on both sides; Tp / Kp = T / K rounded up to the
@@ -36,9 +41,10 @@ __device__ __forceinline__ void wgs_split(float x, __bf16& hi, __bf16& lo) {
 }
 
 // ---------------------------------------------------------------------------------------------------- weights
-// One thread = one (k, c), c < Cp: (G w Gt)[p] with the arithmetic of wg_weights_kernel (mode 0), zero for C <= c, then the split.
+// One thread = one (k, c), c < Cp: (G w Gt)[p] with the arithmetic of wg_weights_kernel, zero for C <= c, then the split.  mode 0: w
+// is [K][C][3][3]; mode 1 (data gradient): w is the layer's own [C][K][3][3], read transposed and rotated by 180 degrees.
 __global__ void __launch_bounds__(kBlock)
-wgs_weights_kernel(const float* __restrict__ w, __bf16* __restrict__ U, int K, int C, int Cp) {
+wgs_weights_kernel(const float* __restrict__ w, __bf16* __restrict__ U, int K, int C, int Cp, int mode) {
     const int64_t e = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
     if (e >= static_cast<int64_t>(K) * Cp) return;
     const int k = static_cast<int>(e / Cp), c = static_cast<int>(e - static_cast<int64_t>(k) * Cp);
@@ -46,7 +52,12 @@ wgs_weights_kernel(const float* __restrict__ w, __bf16* __restrict__ U, int K, i
 #pragma unroll
     for (int r = 0; r < 3; ++r)
 #pragma unroll
-        for (int s = 0; s < 3; ++s) g[r][s] = c < C ? w[(static_cast<size_t>(k) * C + c) * 9 + r * 3 + s] : 0.f;
+        for (int s = 0; s < 3; ++s) {
+            float v = 0.f;
+            if (c < C) v = mode == 0 ? w[(static_cast<size_t>(k) * C + c) * 9 + r * 3 + s]
+                                     : w[(static_cast<size_t>(c) * K + k) * 9 + (2 - r) * 3 + (2 - s)];
+            g[r][s] = v;
+        }
     float t[4][3];
 #pragma unroll
     for (int s = 0; s < 3; ++s) {
@@ -74,9 +85,12 @@ wgs_weights_kernel(const float* __restrict__ w, __bf16* __restrict__ U, int K, i
 // ---------------------------------------------------------------------------------------------------- input transform
 // One thread = one tile x eight channels (blockIdx.y = the channel group): per channel 16 bounds-checked loads (the zero padding, odd
 // H / W, the tile tail and the channel tail all read 0) and Bt d B as wg_input_transform_kernel has it; the 16 entries are split and
-// packed, and the thread stores one hi and one lo line per position, lanes along the tiles.
+// packed, and the thread stores one hi and one lo line per position, lanes along the tiles.  MASK: mask is a tensor of x's shape and
+// x is taken as `mask <= 0 ? 0 : x` (aten::threshold_backward(x, mask, 0): a NaN in the mask lets the value pass, a masked-out
+// infinity is a zero), read with x's own index: both loads run along the tiles as x's does.
+template <bool MASK>
 __global__ void __launch_bounds__(kBlock)
-wgs_input_transform_kernel(const float* __restrict__ x, bf16x8* __restrict__ V, const WgGeo g) {
+wgs_input_transform_kernel(const float* __restrict__ x, const float* __restrict__ mask, bf16x8* __restrict__ V, const WgGeo g) {
     const int t = blockIdx.x * kBlock + threadIdx.x;
     if (t >= g.Tp) return;
     const int c8 = blockIdx.y;
@@ -99,7 +113,11 @@ wgs_input_transform_kernel(const float* __restrict__ x, bf16x8* __restrict__ V, 
             for (int q = 0; q < 4; ++q) {
                 const int iy = 2 * ty - 1 + i, ix = 2 * tx - 1 + q;
                 float e = 0.f;
-                if (cv && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W) e = x[plane + static_cast<size_t>(iy) * g.W + ix];
+                if (cv && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W) {
+                    const size_t o = plane + static_cast<size_t>(iy) * g.W + ix;
+                    e = x[o];
+                    if (MASK) e = mask[o] <= 0.f ? 0.f : e;
+                }
                 d[i * 4 + q] = e;
             }
 #pragma unroll
@@ -249,6 +267,31 @@ wgs_output_transform_kernel(const float* __restrict__ M, const float* __restrict
     wg_store_tile(out, g, t, ko, g.K, y, vec);
 }
 
+// The output transform of the loss networks: the epilogues of wg_output_transform_kernel (conv_winograd_gemm.hip).  One thread = one
+// tile x one output channel; under the max-feature-map epilogue two rows of M, k and k + K / 2, both read with the lanes along the tiles.
+__global__ void __launch_bounds__(kBlock)
+wgs_output_apply_kernel(const float* __restrict__ M, const float* __restrict__ bias, float* __restrict__ out, const WgGeo g, int epi,
+                        int vec) {
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= g.T) return;
+    const int ko = blockIdx.y;
+    const int Kout = epi == FFWM_WG_BIAS_MFM ? g.K / 2 : g.K;
+    const size_t pstride = static_cast<size_t>(g.Kp) * g.Tp;
+    const bool use_bias = bias != nullptr && epi != FFWM_WG_NONE;
+    float y[4];
+    wg_tile_of(M + static_cast<size_t>(ko) * g.Tp + t, pstride, use_bias ? bias[ko] : 0.f, y);
+    if (epi == FFWM_WG_BIAS_RELU) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) y[v] = wg_relu_nan(y[v]);
+    } else if (epi == FFWM_WG_BIAS_MFM) {
+        float y2[4];
+        wg_tile_of(M + static_cast<size_t>(ko + Kout) * g.Tp + t, pstride, use_bias ? bias[ko + Kout] : 0.f, y2);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) y[v] = wg_max_nan(y[v], y2[v]);
+    }
+    wg_store_tile(out, g, t, ko, Kout, y, vec);
+}
+
 }  // namespace
 }  // namespace ffwm
 
@@ -289,8 +332,8 @@ extern "C" int64_t ffwm_conv3x3_wg_split_workspace_bytes(int64_t B, int64_t C, i
     return 16 * T * (wg_round_up(C, kWgsStage) + wg_round_up(K, 128)) * 4;
 }
 
-extern "C" int ffwm_conv3x3_wg_split_weights(const void* weight, void* U, int64_t K, int64_t C, int dtype, void* stream) {
-    const char* fn = "ffwm_conv3x3_wg_split_weights";
+// weight -> the split U of one direction.  K / C in the GEMM's terms: U has K rows and reduces over C.
+static int wgs_weights_call(const char* fn, const void* weight, void* U, int64_t K, int64_t C, int mode, int dtype, void* stream) {
     FFWM_REQUIRE(dtype == FFWM_F32, FFWM_ERR_DTYPE, "%s: float32 only (split into bf16 terms for the bf16 MFMA)", fn);
     FFWM_REQUIRE(weight && U, FFWM_ERR_ARG, "%s: NULL tensor pointer", fn);
     FFWM_REQUIRE(K > 0 && C > 0, FFWM_ERR_ARG, "%s: sizes must be positive", fn);
@@ -301,8 +344,17 @@ extern "C" int ffwm_conv3x3_wg_split_weights(const void* weight, void* U, int64_
     LaunchScope ls("conv_wgs_weights", st, 4.0 * (9.0 * K * C + 16.0 * K * Cp));
     hipLaunchKernelGGL(wgs_weights_kernel, dim3(static_cast<unsigned>((K * Cp + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
                        static_cast<const float*>(weight), static_cast<__bf16*>(U), static_cast<int>(K), static_cast<int>(C),
-                       static_cast<int>(Cp));
+                       static_cast<int>(Cp), mode);
     return check_launch(fn);
+}
+
+extern "C" int ffwm_conv3x3_wg_split_weights(const void* weight, void* U, int64_t K, int64_t C, int dtype, void* stream) {
+    return wgs_weights_call("ffwm_conv3x3_wg_split_weights", weight, U, K, C, 0, dtype, stream);
+}
+
+extern "C" int ffwm_conv3x3_wg_split_weights_dgrad(const void* weight, void* U, int64_t K, int64_t C, int dtype, void* stream) {
+    // the data gradient of a Conv2d(C, K) is a convolution with C output rows that reduces over K
+    return wgs_weights_call("ffwm_conv3x3_wg_split_weights_dgrad", weight, U, C, K, 1, dtype, stream);
 }
 
 extern "C" int ffwm_conv3x3_wg_split_tile(int64_t B, int64_t C, int64_t H, int64_t W, int64_t K) {
@@ -310,23 +362,18 @@ extern "C" int ffwm_conv3x3_wg_split_tile(int64_t B, int64_t C, int64_t H, int64
     return wgs_plan(B, C, H, W, K, 0).tile;
 }
 
-extern "C" int ffwm_conv3x3_wg_split_forward(const void* input, const void* U, const void* bias, void* output, void* workspace,
-                                             int64_t B, int64_t C, int64_t H, int64_t W, int64_t K, int epilogue, double negative_slope,
-                                             int tile, int dtype, void* stream) {
-    const char* fn = "ffwm_conv3x3_wg_split_forward";
-    FFWM_REQUIRE(dtype == FFWM_F32, FFWM_ERR_DTYPE, "%s: float32 only (split into bf16 terms for the bf16 MFMA)", fn);
-    FFWM_REQUIRE(input && U && output && workspace, FFWM_ERR_ARG, "%s: NULL tensor pointer", fn);
-    FFWM_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && K > 0, FFWM_ERR_ARG, "%s: sizes must be positive", fn);
-    const int epi = epilogue;
-    FFWM_REQUIRE(epi >= kWgsNone && epi <= kWgsBiasLrelu, FFWM_ERR_ARG,
-                 "%s: epilogue must be 0 (none), 1 (bias) or 2 (bias, LeakyReLU)", fn);
-    FFWM_REQUIRE(epi == kWgsNone || bias, FFWM_ERR_ARG, "%s: the bias epilogues need a bias", fn);
+// What the two entry points share: the checks that do not depend on the epilogue's code, then the three launches.  apply: the
+// epilogue codes of the fp32 route (FFWM_WG_*) and the ReLU mask; else FFWM_WGS_* with its LeakyReLU slope.
+static int wgs_call(const char* fn, bool apply, const void* input, const void* U, const void* bias, void* output, void* workspace,
+                    int64_t B, int64_t C, int64_t H, int64_t W, int64_t K, int epi, double negative_slope, const void* relu_mask,
+                    int tile, void* stream) {
     FFWM_REQUIRE(tile == 0 || tile == 64 || tile == 128, FFWM_ERR_ARG, "%s: tile must be 0 (the plan's), 64 or 128", fn);
     FFWM_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0 && reinterpret_cast<uintptr_t>(U) % 16 == 0, FFWM_ERR_ARG,
                  "%s: U and the workspace must be 16-byte aligned", fn);
     FFWM_REQUIRE(B * C * H * W < (1LL << 31) && B * K * H * W < (1LL << 31), FFWM_ERR_SIZE, "%s: a tensor beyond 2^31 elements", fn);
     const WgsPlan p = wgs_plan(B, C, H, W, K, tile);
-    FFWM_REQUIRE(p.Tp < (1LL << 30) && p.Cp / 8 <= 65535 && K <= 65535 && 16 * p.KT * p.TTn < (1LL << 31), FFWM_ERR_SIZE,
+    const int64_t Kout = apply && epi == FFWM_WG_BIAS_MFM ? K / 2 : K;
+    FFWM_REQUIRE(p.Tp < (1LL << 30) && p.Cp / 8 <= 65535 && Kout <= 65535 && 16 * p.KT * p.TTn < (1LL << 31), FFWM_ERR_SIZE,
                  "%s: too many tiles or channels", fn);
     WgGeo g;
     g.C = static_cast<int>(C); g.C4 = static_cast<int>(p.Cp / 4);
@@ -338,9 +385,14 @@ extern "C" int ffwm_conv3x3_wg_split_forward(const void* input, const void* U, c
     float* M = reinterpret_cast<float*>(V + p.v_bytes);
     const double act = static_cast<double>(B) * H * W;
     {
-        LaunchScope ls("conv_wgs_in", st, 4.0 * act * C + static_cast<double>(p.v_bytes));
-        hipLaunchKernelGGL(wgs_input_transform_kernel, dim3(static_cast<unsigned>((p.Tp + kBlock - 1) / kBlock), static_cast<unsigned>(p.Cp / 8)),
-                           dim3(kBlock), 0, st, static_cast<const float*>(input), reinterpret_cast<bf16x8*>(V), g);
+        LaunchScope ls("conv_wgs_in", st, 4.0 * act * C * (relu_mask ? 2.0 : 1.0) + static_cast<double>(p.v_bytes));
+        const dim3 grid(static_cast<unsigned>((p.Tp + kBlock - 1) / kBlock), static_cast<unsigned>(p.Cp / 8));
+        if (relu_mask)
+            hipLaunchKernelGGL(wgs_input_transform_kernel<true>, grid, dim3(kBlock), 0, st, static_cast<const float*>(input),
+                               static_cast<const float*>(relu_mask), reinterpret_cast<bf16x8*>(V), g);
+        else
+            hipLaunchKernelGGL(wgs_input_transform_kernel<false>, grid, dim3(kBlock), 0, st, static_cast<const float*>(input),
+                               static_cast<const float*>(nullptr), reinterpret_cast<bf16x8*>(V), g);
     }
     if (int rc = check_launch(fn)) return rc;
     {
@@ -356,11 +408,44 @@ extern "C" int ffwm_conv3x3_wg_split_forward(const void* input, const void* U, c
     }
     if (int rc = check_launch(fn)) return rc;
     {
-        LaunchScope ls("conv_wgs_out", st, 4.0 * (16.0 * K * p.T + act * K));
+        LaunchScope ls("conv_wgs_out", st, 4.0 * (16.0 * K * p.T + act * Kout));
         const int vec = W % 2 == 0 && reinterpret_cast<uintptr_t>(output) % 8 == 0;
-        hipLaunchKernelGGL(wgs_output_transform_kernel, dim3(static_cast<unsigned>((p.T + kBlock - 1) / kBlock), static_cast<unsigned>(K)),
-                           dim3(kBlock), 0, st, M, static_cast<const float*>(bias), static_cast<float*>(output), g, epi,
-                           static_cast<float>(negative_slope), vec);
+        const dim3 grid(static_cast<unsigned>((p.T + kBlock - 1) / kBlock), static_cast<unsigned>(Kout));
+        if (apply)
+            hipLaunchKernelGGL(wgs_output_apply_kernel, grid, dim3(kBlock), 0, st, M, static_cast<const float*>(bias),
+                               static_cast<float*>(output), g, epi, vec);
+        else
+            hipLaunchKernelGGL(wgs_output_transform_kernel, grid, dim3(kBlock), 0, st, M, static_cast<const float*>(bias),
+                               static_cast<float*>(output), g, epi, static_cast<float>(negative_slope), vec);
     }
     return check_launch(fn);
+}
+
+extern "C" int ffwm_conv3x3_wg_split_forward(const void* input, const void* U, const void* bias, void* output, void* workspace,
+                                             int64_t B, int64_t C, int64_t H, int64_t W, int64_t K, int epilogue, double negative_slope,
+                                             int tile, int dtype, void* stream) {
+    const char* fn = "ffwm_conv3x3_wg_split_forward";
+    FFWM_REQUIRE(dtype == FFWM_F32, FFWM_ERR_DTYPE, "%s: float32 only (split into bf16 terms for the bf16 MFMA)", fn);
+    FFWM_REQUIRE(input && U && output && workspace, FFWM_ERR_ARG, "%s: NULL tensor pointer", fn);
+    FFWM_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && K > 0, FFWM_ERR_ARG, "%s: sizes must be positive", fn);
+    const int epi = epilogue;
+    FFWM_REQUIRE(epi >= kWgsNone && epi <= kWgsBiasLrelu, FFWM_ERR_ARG,
+                 "%s: epilogue must be 0 (none), 1 (bias) or 2 (bias, LeakyReLU)", fn);
+    FFWM_REQUIRE(epi == kWgsNone || bias, FFWM_ERR_ARG, "%s: the bias epilogues need a bias", fn);
+    return wgs_call(fn, false, input, U, bias, output, workspace, B, C, H, W, K, epi, negative_slope, nullptr, tile, stream);
+}
+
+extern "C" int ffwm_conv3x3_wg_split_apply(const void* input, const void* U, const void* bias, void* output, void* workspace,
+                                           int64_t B, int64_t C, int64_t H, int64_t W, int64_t K, int epilogue, const void* relu_mask,
+                                           int tile, int dtype, void* stream) {
+    const char* fn = "ffwm_conv3x3_wg_split_apply";
+    FFWM_REQUIRE(dtype == FFWM_F32, FFWM_ERR_DTYPE, "%s: float32 only (split into bf16 terms for the bf16 MFMA)", fn);
+    FFWM_REQUIRE(input && U && output && workspace, FFWM_ERR_ARG, "%s: NULL tensor pointer", fn);
+    FFWM_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && K > 0, FFWM_ERR_ARG, "%s: sizes must be positive", fn);
+    const int epi = epilogue;
+    FFWM_REQUIRE(epi >= FFWM_WG_NONE && epi <= FFWM_WG_BIAS_MFM, FFWM_ERR_ARG,
+                 "%s: epilogue must be 0 (none), 1 (bias), 2 (bias, relu) or 3 (bias, max-feature-map)", fn);
+    FFWM_REQUIRE(epi == FFWM_WG_NONE || bias, FFWM_ERR_ARG, "%s: the bias epilogues need a bias", fn);
+    FFWM_REQUIRE(epi != FFWM_WG_BIAS_MFM || K % 2 == 0, FFWM_ERR_ARG, "%s: the max-feature-map epilogue needs an even K", fn);
+    return wgs_call(fn, true, input, U, bias, output, workspace, B, C, H, W, K, epi, 0.0, relu_mask, tile, stream);
 }

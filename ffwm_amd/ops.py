@@ -928,13 +928,21 @@ def conv3x3_wg_tile(B, C, H, W, K):
 WG_SPLIT_EPILOGUES = {"none": 0, "bias": 1, "lrelu": 2}
 
 
-def conv3x3_wg_split_weights(weight):
-    """U = G w G^T of a FROZEN Conv2d(C, K, 3, 1, 1) weight [K, C, 3, 3], every entry split in two bf16 terms, for conv3x3_wg_split.
-    One launch; made once per layer.  A float32 tensor that holds the bf16 halves (ffwm_conv3x3_wg_split_weights_bytes)."""
+def conv3x3_wg_split_weights(weight, data_gradient=False):
+    """U = G w G^T of a FROZEN Conv2d(C, K, 3, 1, 1) weight [K, C, 3, 3], every entry split in two bf16 terms, for conv3x3_wg_split /
+    conv3x3_wg_split_frozen: the forward's, or (data_gradient) the data gradient's -- the weight read transposed and rotated, bit for
+    bit the forward's U of weight.transpose(0, 1).flip(2, 3).  One launch; made once per layer and direction.  A float32 tensor that
+    holds the bf16 halves (ffwm_conv3x3_wg_split_weights_bytes)."""
     if not (weight.is_cuda and weight.dtype == torch.float32 and weight.is_contiguous() and weight.dim() == 4 and tuple(weight.shape[2:]) == (3, 3)):
         raise ValueError("conv3x3_wg_split_weights: a contiguous float32 [K, C, 3, 3] weight on the GPU")
     K, C = weight.shape[0], weight.shape[1]
     lib = _lib.load()
+    if data_gradient:
+        U = weight.new_empty((lib.ffwm_conv3x3_wg_split_weights_bytes(C, K) // 4,))
+        with _on_device(weight) as stream:
+            _lib.check(lib.ffwm_conv3x3_wg_split_weights_dgrad(_ptr(weight), _ptr(U), K, C, _lib.F32, stream),
+                       "ffwm_conv3x3_wg_split_weights_dgrad")
+        return U
     U = weight.new_empty((lib.ffwm_conv3x3_wg_split_weights_bytes(K, C) // 4,))
     with _on_device(weight) as stream:
         _lib.check(lib.ffwm_conv3x3_wg_split_weights(_ptr(weight), _ptr(U), K, C, _lib.F32, stream), "ffwm_conv3x3_wg_split_weights")
@@ -979,6 +987,51 @@ def conv3x3_wg_split(x, U, bias, epilogue, slope=0.2, out=None, K=None, tile=0, 
     with _on_device(x) as stream:
         _lib.check(lib.ffwm_conv3x3_wg_split_forward(_ptr(x), _ptr(U), _ptr(bias), _ptr(out), _ptr(workspace), B, C, H, W, K, epi,
                                                      float(slope), int(tile), _dtype_code(x), stream), "ffwm_conv3x3_wg_split_forward")
+    return out
+
+
+def conv3x3_wg_split_frozen(x, U, bias, epilogue, relu_mask=None, out=None, K=None, tile=0, workspace=None):
+    """conv3x3_wg_split for the frozen loss networks of the train step, with the epilogue names of conv3x3_wg: "none", "bias", "relu"
+    (bias + ReLU) or "mfm" (bias + max-feature-map: [B, K / 2, H, W]).  relu_mask: a tensor of x's shape; x is read as
+    aten::threshold_backward(x, relu_mask, 0) (the data gradient behind a ReLU; U of conv3x3_wg_split_weights(w, data_gradient=True)).
+    K: the output channels before the epilogue (default: bias.numel()).  tile (tests): 64 / 128 fixes the GEMM tile.  workspace: a
+    float32 tensor of at least ffwm_conv3x3_wg_split_workspace_bytes, else allocated."""
+    _check("conv3x3_wg_split_frozen", x, relu_mask, out)
+    for t in (U, bias, workspace):
+        if t is not None and (t.device != x.device or t.dtype != x.dtype or not t.is_contiguous()):
+            raise ValueError("conv3x3_wg_split_frozen: U, bias and workspace must be contiguous tensors of the input's device and dtype")
+    if x.dtype != torch.float32:
+        raise TypeError("conv3x3_wg_split_frozen: float32 only")
+    B, C, H, W = x.shape
+    if K is None:
+        if bias is None:
+            raise ValueError("conv3x3_wg_split_frozen: K is needed when there is no bias")
+        K = bias.numel()
+    lib = _lib.load()
+    if U.numel() * 4 != lib.ffwm_conv3x3_wg_split_weights_bytes(K, C):
+        raise ValueError("conv3x3_wg_split_frozen: U does not belong to a layer with %d input and %d output channels" % (C, K))
+    epi = WG_EPILOGUES[epilogue]
+    if epi and bias is None:
+        raise ValueError("conv3x3_wg_split_frozen: the %s epilogue needs a bias" % epilogue)
+    if bias is not None and bias.numel() != K:
+        raise ValueError("conv3x3_wg_split_frozen: bias must be a contiguous vector of %d elements" % K)
+    if relu_mask is not None and (relu_mask.shape != x.shape or not relu_mask.is_contiguous()):
+        raise ValueError("conv3x3_wg_split_frozen: relu_mask must be contiguous and of x's shape")
+    if epi == 3 and K % 2:
+        raise ValueError("conv3x3_wg_split_frozen: the mfm epilogue needs an even K")
+    shape = (B, K // 2 if epi == 3 else K, H, W)
+    if out is None:
+        out = x.new_empty(shape)
+    elif tuple(out.shape) != shape:
+        raise ValueError("conv3x3_wg_split_frozen: out has the wrong shape")
+    need = lib.ffwm_conv3x3_wg_split_workspace_bytes(B, C, H, W, K) // 4
+    if workspace is None:
+        workspace = x.new_empty((need,))
+    elif workspace.numel() < need:
+        raise ValueError("conv3x3_wg_split_frozen: the workspace is too small")
+    with _on_device(x) as stream:
+        _lib.check(lib.ffwm_conv3x3_wg_split_apply(_ptr(x), _ptr(U), _ptr(bias), _ptr(out), _ptr(workspace), B, C, H, W, K, epi,
+                                                   _ptr(relu_mask), int(tile), _dtype_code(x), stream), "ffwm_conv3x3_wg_split_apply")
     return out
 
 

@@ -167,9 +167,16 @@ class FFWMTrainer(object):
     def __init__(self, device, world_size=1, seed=0, titers=0, bucket_bytes=64 << 20, warp=None,
                  warp_flipcat=None, ngf=64, capturable=False, fused_spectral_norm=None, batched_losses=True,
                  mfma_wgrad=None, flat_adam=None, fused_bn=None, mfma_fwd=None, fused_l1=None, segmented_backward=False,
-                 force_collectives=False, crop=False):
+                 force_collectives=False, crop=False, loss_precision="fp32"):
         self.device = torch.device(device)
         self.titers = titers
+        # "bf16x3": the frozen 3 x 3 layers of the loss networks that conv.WGS_TABLE names run their 16 Winograd GEMMs on the bf16 MFMA
+        # with hi / lo split operands (csrc/conv_winograd_gemm_split.hip), forward and data gradient; "fp32": the step as it was
+        if loss_precision not in ("fp32", "bf16x3"):
+            raise ValueError("FFWMTrainer: loss_precision must be \"fp32\" or \"bf16x3\", got %r" % (loss_precision,))
+        if loss_precision == "bf16x3" and self.device.type != "cuda":
+            raise ValueError("FFWMTrainer: loss_precision=\"bf16x3\" needs a GPU (the split Winograd route is a HIP kernel)")
+        self.loss_precision = loss_precision
         # train_ffwm.py --crop (models/ffwm_model.py:43): every LightCNN input of the step is the centre-face crop
         self.crop = bool(crop)
         # data parallelism is live when there are several ranks (force_collectives: also in a one-rank process group -- the
@@ -256,7 +263,10 @@ class FFWMTrainer(object):
         self.wg_weight_bytes = 0
         if self.device.type == "cuda":
             # the frozen loss networks' small-plane 3x3 layers: transformed weights of the batched-GEMM Winograd route, once (conv.py)
-            from .conv import wg_prepare
+            from .conv import wg_prepare, wg_set_precision
+            if loss_precision != "fp32":
+                wg_set_precision(self.vgg, loss_precision)
+                wg_set_precision(self.lightCNN, loss_precision)
             self.wg_weight_bytes = wg_prepare(self.vgg) + wg_prepare(self.lightCNN)
 
         flow_params = [p for net in (self.flowNetF, self.flowNetB) for n, p in net.named_parameters()

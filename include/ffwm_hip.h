@@ -635,6 +635,19 @@ int ffwm_conv3x3_wg_split_tile(int64_t B, int64_t C, int64_t H, int64_t W, int64
 int ffwm_conv3x3_wg_split_forward(const void* input, const void* U, const void* bias, void* output, void* workspace,
                                   int64_t B, int64_t C, int64_t H, int64_t W, int64_t K, int epilogue, double negative_slope,
                                   int tile, int dtype, void* stream);
+/* The same GEMM for the FROZEN loss networks of the train step (VGG19, LightCNN under autograd; loss_precision="bf16x3"): the data
+ * gradient with its ReLU mask and the epilogues of the fp32 route.  Bounds: tests/wino_split_train_cases.py.
+ *   ffwm_conv3x3_wg_split_weights_dgrad: the layer's own weight [K, C, 3, 3], read transposed and rotated by 180 degrees -> the
+ *     split U of the data gradient (C output rows, reduction over K rounded up to 32), ffwm_conv3x3_wg_split_weights_bytes(C, K)
+ *     bytes: bit for bit ffwm_conv3x3_wg_split_weights of weight.transpose(0, 1).flip(2, 3).
+ *   ffwm_conv3x3_wg_split_apply: ffwm_conv3x3_wg_split_forward with the epilogue codes FFWM_WG_* (ReLU by torch.relu's rule: NaN
+ *     stays NaN, -inf gives 0; max-feature-map: maximum(a, b) with ATen's NaN rule of rows k and k + K / 2, output [B, K / 2, H, W],
+ *     K even) and relu_mask (NULL, or a tensor of the input's shape: the input is read as `mask <= 0 ? 0 : x`, so a NaN in the mask
+ *     lets the value pass and a masked-out infinity or NaN is a zero).  Workspace, plan and tile as ffwm_conv3x3_wg_split_forward. */
+int ffwm_conv3x3_wg_split_weights_dgrad(const void* weight, void* U, int64_t K, int64_t C, int dtype, void* stream);
+int ffwm_conv3x3_wg_split_apply(const void* input, const void* U, const void* bias, void* output, void* workspace,
+                                int64_t B, int64_t C, int64_t H, int64_t W, int64_t K, int epilogue, const void* relu_mask,
+                                int tile, int dtype, void* stream);
 
 /* One Adam step (no weight decay, no amsgrad: torch.optim.Adam as models/ffwm_model.py:46-49 and
  * models/flownet_model.py:33 construct it) over FLAT float32 arrays of n elements, 16-byte aligned: parameters,
