@@ -52,6 +52,10 @@ _SIGNATURES = {
     "ffwm_conv3x3_winograd_forward": [_p, _p, _p, _p, _p] + [_i64] * 5 + [_i, _i, ctypes.c_double, _i, _p],
     "ffwm_adam_step": [_p, _p, _p, _p, _i64] + [ctypes.c_double] * 4 + [_i64, _i, _p],
     "ffwm_adam_step_device": [_p, _p, _p, _p, _i64] + [ctypes.c_double] * 4 + [_p, _i, _p],
+    # (grads, n, seg_end, n_seg, workspace, workspace_bytes, record, dtype, stream)
+    "ffwm_grad_health": [_p, _i64, _p, _i, _p, ctypes.c_size_t, _p, _i, _p],
+    # (params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, state, record, n_seg, max_norm, skip_nonfinite, guard, dtype, stream)
+    "ffwm_adam_step_guarded": [_p, _p, _p, _p, _i64] + [ctypes.c_double] * 4 + [_p, _p, _i, ctypes.c_double, _i, _p, _i, _p],
     # (params, grads, momentum_buf, n, seg_end, seg_group, n_seg, group_lr, group_wd, n_groups, momentum, dtype, stream)
     "ffwm_sgd_step": [_p, _p, _p, _i64, _p, _p, _i, _p, _p, _i, ctypes.c_double, _i, _p],
     # (logits, target, out, row_loss, rank, grad_logits, skipped, workspace, B, N, dtype, stream)
@@ -125,7 +129,8 @@ EXPORTS = sorted(list(_SIGNATURES) + ["ffwm_last_error", "ffwm_conv3x3_winograd_
                                       "ffwm_sampling_correctness_workspace_bytes", "ffwm_landmark_loss_workspace_bytes",
                                       "ffwm_cosine_topk_workspace_bytes", "ffwm_softmax_xent_workspace_bytes",
                                       "ffwm_conv3x3_wg_weights_bytes", "ffwm_conv3x3_wg_workspace_bytes", "ffwm_visuals_workspace_bytes",
-                                      "ffwm_conv3x3_wg_split_weights_bytes", "ffwm_conv3x3_wg_split_workspace_bytes"])
+                                      "ffwm_conv3x3_wg_split_weights_bytes", "ffwm_conv3x3_wg_split_workspace_bytes",
+                                      "ffwm_grad_health_workspace_bytes"])
 
 
 class FFWMError(RuntimeError):
@@ -172,6 +177,8 @@ def load():
     lib.ffwm_conv3x3_wg_split_workspace_bytes.restype = _i64
     lib.ffwm_visuals_workspace_bytes.argtypes = [_p, _i]
     lib.ffwm_visuals_workspace_bytes.restype = _i64
+    lib.ffwm_grad_health_workspace_bytes.argtypes = [_i64, _i]
+    lib.ffwm_grad_health_workspace_bytes.restype = ctypes.c_size_t
     lib.ffwm_last_error.argtypes = []
     lib.ffwm_last_error.restype = ctypes.c_char_p
     got = lib.ffwm_abi_version()

@@ -656,6 +656,50 @@ def softmax_xent(logits, target, want_grad=True, out_grad=None):
     return out, row_loss, rank, grad, skipped
 
 
+# ---------------------------------------------------------------- gradient health (csrc/grad_health.hip)
+GRAD_HEALTH_CHUNK = 8192           # FFWM_GRAD_HEALTH_CHUNK of include/ffwm_hip.h (tests/test_grad_health_cpu.py holds the two together)
+GRAD_HEALTH_MAX_SEGMENTS = 16
+
+
+def grad_health_workspace_doubles(n, n_seg):
+    """The doubles ffwm_grad_health wants as workspace for n elements in n_seg segments."""
+    return _lib.load().ffwm_grad_health_workspace_bytes(n, n_seg) // 8
+
+
+def grad_health(flat, seg_end, record=None, workspace=None):
+    """-> record [n_seg, 4] float64 on the device: per segment of the flat float32 gradient array, over its FINITE elements, sum g^2
+    and max |g|, then the count of non-finite elements and the element count.  seg_end: an int64 DEVICE tensor of ascending ends in
+    elements (a list is copied to the device), the last one flat.numel(), every other one a multiple of 4; at most 16.  record and
+    workspace (float64, grad_health_workspace_doubles(n, n_seg) elements) are made when not given; only they are written.  Squares and
+    sums in double, no atomics, the same bits on every call (csrc/grad_health.hip states the order of summation)."""
+    name = "grad_health"
+    if not torch.is_tensor(flat) or flat.dim() != 1:
+        raise ValueError("%s: a flat 1-D tensor expected" % name)
+    if not flat.is_cuda:
+        raise NotImplementedError("%s: ffwm_amd ops run on the GPU only (got a %s tensor)" % (name, flat.device))
+    if flat.dtype != torch.float32 or not flat.is_contiguous() or flat.numel() == 0:
+        raise ValueError("%s: a contiguous float32 tensor with at least one element expected" % name)
+    if not torch.is_tensor(seg_end):
+        seg_end = torch.tensor(list(seg_end), dtype=torch.int64, device=flat.device)
+    if seg_end.dtype != torch.int64 or seg_end.dim() != 1 or seg_end.device != flat.device or not seg_end.is_contiguous():
+        raise ValueError("%s: seg_end must be a contiguous 1-D int64 tensor on the gradients' device" % name)
+    n, n_seg = flat.numel(), seg_end.numel()
+    if not 1 <= n_seg <= GRAD_HEALTH_MAX_SEGMENTS:
+        raise ValueError("%s: 1 .. %d segments, got %d" % (name, GRAD_HEALTH_MAX_SEGMENTS, n_seg))
+    if record is None:
+        record = torch.empty(n_seg, 4, dtype=torch.float64, device=flat.device)
+    if workspace is None:
+        workspace = torch.empty(grad_health_workspace_doubles(n, n_seg), dtype=torch.float64, device=flat.device)
+    for what, t, least in (("record", record, 4 * n_seg), ("workspace", workspace, 0)):
+        if t.dtype != torch.float64 or t.device != flat.device or not t.is_contiguous() or t.numel() < least:
+            raise ValueError("%s: %s must be a contiguous float64 tensor on the gradients' device%s"
+                             % (name, what, " with 4 values per segment" if least else ""))
+    with _on_device(flat) as stream:
+        _lib.check(_lib.load().ffwm_grad_health(_ptr(flat), n, _ptr(seg_end), n_seg, _ptr(workspace), workspace.numel() * 8, _ptr(record),
+                                                _lib.F32, stream), "ffwm_grad_health")
+    return record
+
+
 # ---------------------------------------------------------------- conv weight gradient (MFMA)
 def conv3x3_wgrad_supported(input, grad_output):
     """Shapes the MFMA weight-gradient kernel takes: float32 NCHW, W a multiple of 64, below 4 GiB."""

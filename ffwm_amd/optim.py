@@ -8,14 +8,72 @@ Like the reference's checkpoints (models/base_model.py:save_networks), optimizer
 
 FlatSGD: the same for torch.optim.SGD with momentum and one (learning rate, weight decay) per parameter group
 (lightcnn/finetune.py:74-90), csrc/sgd.hip.
+
+Gradient health (FlatAdam's monitor / skip_nonfinite / max_grad_norm, all off by default): the step becomes one streaming reduction
+over the optimizer's slice of the flat gradients (csrc/grad_health.hip: per segment sum g^2, max |g|, non-finite count) and an Adam
+step that reads its decision -- apply, apply clipped, or skip -- from device memory (ffwm_adam_step_guarded), so both sit inside a
+captured step.  The guard protects the parameters and both moment arrays.  It restores nothing else: the BatchNorm running
+statistics were already updated by the forward pass of the bad step.
 """
+import math
+
 import torch
 
 from . import _lib
 
+MAX_HEALTH_SEGMENTS = 16          # FFWM_GRAD_HEALTH_MAX_SEGMENTS (include/ffwm_hip.h)
+_HEALTH_KEYS = ("scale", "skipped", "steps_skipped", "steps_seen", "steps_applied")
+
+
+def clip_coefficient(sumsq, max_norm):
+    """The factor a clipped step multiplies its gradients by, from the sum of their squares: torch.nn.utils.clip_grad_norm_'s
+    min(1, max_norm / (sqrt(sumsq) + 1e-6)) in double; 1.0 when max_norm is None or <= 0 (no clipping).  The kernel
+    (csrc/adam.hip: adam_guard_advance_kernel) computes the same expression and rounds it once to float32."""
+    if max_norm is None or max_norm <= 0:
+        return 1.0
+    return min(1.0, float(max_norm) / (math.sqrt(sumsq) + 1e-6))
+
+
+def _health_segments(segments, order, offset, lo, n):
+    """[(name, end)] from FlatAdam's ``segments`` (a list of (name, params)): they must tile ``order`` -- the optimizer's parameters
+    in the reducer's order -- segment by segment.  A segment ends where the next one's first parameter begins, the last one at n."""
+    if segments is None:
+        return [("all", n)]
+    segments = [(name, [p for p in ps if p.requires_grad]) for name, ps in segments]
+    if len(segments) > MAX_HEALTH_SEGMENTS:
+        raise ValueError("FlatAdam: at most %d segments (csrc/grad_health.hip), got %d" % (MAX_HEALTH_SEGMENTS, len(segments)))
+    names = [name for name, _ in segments]
+    if len(set(names)) != len(names) or set(names) & set(_HEALTH_KEYS) or not all(isinstance(k, str) for k in names):
+        raise ValueError("FlatAdam: segment names must be distinct strings other than %s" % ", ".join(_HEALTH_KEYS))
+    walked, own = [], set(map(id, order))
+    for name, ps in segments:
+        if not ps:
+            raise ValueError("FlatAdam: segment %r has no trainable parameter" % name)
+        if any(id(p) not in own for p in ps):
+            raise ValueError("FlatAdam: segment %r holds a parameter that is not the optimizer's" % name)
+        walked += sorted(ps, key=lambda p: offset[p][0])
+    if list(map(id, walked)) != list(map(id, order)):
+        raise ValueError("FlatAdam: the segments do not tile the optimizer's parameter range in the reducer's order")
+    starts = [min(offset[p][0] for p in ps) - lo for _, ps in segments]
+    return list(zip(names, starts[1:] + [n]))
+
 
 class FlatAdam(object):
-    def __init__(self, params, reducer, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, capturable=False):
+    """``monitor``, ``skip_nonfinite``, ``max_grad_norm`` (all off by default; with all three off step() is the one launch it always
+    was, and nothing below is allocated):
+      monitor         every step() first measures the optimizer's gradients (ffwm_grad_health); health() reports them.
+      skip_nonfinite  a step whose gradients hold a NaN or an inf changes neither the parameters nor the moments nor the step count
+                      of the bias corrections; the decision is taken on the device, so it also holds for every replay of a captured
+                      step.  BatchNorm running statistics the forward pass of that step already wrote are NOT restored.
+      max_grad_norm   clip by the global norm over the optimizer's whole range, torch.nn.utils.clip_grad_norm_'s coefficient
+                      (clip_coefficient); needs skip_nonfinite.  The gradient array itself is not rescaled.
+      segments        [(name, params), ...] tiling the optimizer's parameters in the reducer's order (at most 16): the ranges
+                      health() reports on; one segment "all" by default.
+    Any of the three turns the step into ffwm_grad_health + ffwm_adam_step_guarded, with the step counter on the device whatever
+    ``capturable`` says; record, workspace, guard and the segment table are allocated here, once."""
+
+    def __init__(self, params, reducer, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, capturable=False, monitor=False, skip_nonfinite=False,
+                 max_grad_norm=None, segments=None):
         params = [p for p in params if p.requires_grad]
         if reducer.flat is None or not params:
             raise ValueError("FlatAdam needs a reducer with one flat gradient array and at least one parameter")
@@ -29,6 +87,17 @@ class FlatAdam(object):
         self.reducer = reducer
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
         n = self.hi - self.lo
+        # the health options are checked before anything touches a device
+        if max_grad_norm is not None and not skip_nonfinite:
+            raise ValueError("FlatAdam: max_grad_norm needs skip_nonfinite=True (a clip over a non-finite norm has no meaning)")
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0:
+            raise ValueError("FlatAdam: max_grad_norm must be >= 0 (0 or None: no clipping), got %r" % (max_grad_norm,))
+        self.monitor, self.skip_nonfinite = bool(monitor), bool(skip_nonfinite)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.guarded = self.monitor or self.skip_nonfinite or self.max_grad_norm is not None
+        self.segments = None
+        if self.guarded or segments is not None:
+            self.segments = _health_segments(segments, sorted(params, key=lambda p: reducer.offset[p][0]), reducer.offset, self.lo, n)
         dev, dt = reducer.flat.device, reducer.flat.dtype
         if dt != torch.float32 or dev.type != "cuda":
             raise NotImplementedError("FlatAdam runs on float32 CUDA parameters only (csrc/adam.hip)")
@@ -48,7 +117,15 @@ class FlatAdam(object):
         self.capturable = bool(capturable)
         # state[0] step counter, state[1..2] scratch, state[3] the current learning rate (csrc/adam.hip: it overrides the kernel argument
         # a captured graph has baked in)
-        self.state = torch.zeros(4, device=dev, dtype=torch.float64) if self.capturable else None
+        self.state = torch.zeros(4, device=dev, dtype=torch.float64) if (self.capturable or self.guarded) else None
+        # the health pass: [record (4 per segment) | guard (6)] in one array, so that health() is one copy; a captured step holds these addresses
+        self.seg_end = self.record = self.guard = self.workspace = self._health = None
+        if self.guarded:
+            n_seg = len(self.segments)
+            self.seg_end = torch.tensor([e for _, e in self.segments], dtype=torch.int64, device=dev)
+            self._health = torch.zeros(4 * n_seg + 6, device=dev, dtype=torch.float64)
+            self.record, self.guard = self._health[:4 * n_seg], self._health[4 * n_seg:]
+            self.workspace = torch.empty(_lib.load().ffwm_grad_health_workspace_bytes(n, n_seg) // 8, device=dev, dtype=torch.float64)
         if self.state is not None:
             self.state[3] = -1.0          # no learning-rate override yet (0.0 is a legitimate rate: the sentinel is negative)
         # torch.optim's interface for schedulers (base_model.update_learning_rate: StepLR / lambda rules write param_groups[i]['lr'])
@@ -71,7 +148,7 @@ class FlatAdam(object):
             lr = self._lr_seen
         self.lr = self._lr_seen = lr
         self.param_groups[0]["lr"] = lr
-        if self.capturable and lr != self._lr_on_device and not torch.cuda.is_current_stream_capturing():
+        if self.state is not None and lr != self._lr_on_device and not torch.cuda.is_current_stream_capturing():
             self.state[3:4].fill_(lr)
             self._lr_on_device = lr
         return lr
@@ -85,7 +162,17 @@ class FlatAdam(object):
         if cur != dev:
             torch.cuda.set_device(dev)
         try:
-            if self.capturable:
+            if self.guarded:
+                lib, stream = _lib.load(), torch.cuda.current_stream(dev).cuda_stream
+                n_seg = len(self.segments)
+                _lib.check(lib.ffwm_grad_health(g.data_ptr(), self.n, self.seg_end.data_ptr(), n_seg, self.workspace.data_ptr(),
+                                                self.workspace.numel() * 8, self.record.data_ptr(), _lib.F32, stream), "ffwm_grad_health")
+                _lib.check(lib.ffwm_adam_step_guarded(self.params.data_ptr(), g.data_ptr(), self.exp_avg.data_ptr(),
+                                                      self.exp_avg_sq.data_ptr(), self.n, self.lr, self.betas[0], self.betas[1], self.eps,
+                                                      self.state.data_ptr(), self.record.data_ptr(), n_seg, self.max_grad_norm or 0.0,
+                                                      int(self.skip_nonfinite), self.guard.data_ptr(), _lib.F32, stream),
+                           "ffwm_adam_step_guarded")
+            elif self.capturable:
                 _lib.check(_lib.load().ffwm_adam_step_device(self.params.data_ptr(), g.data_ptr(), self.exp_avg.data_ptr(),
                                                              self.exp_avg_sq.data_ptr(), self.n, self.lr, self.betas[0], self.betas[1],
                                                              self.eps, self.state.data_ptr(), _lib.F32,
@@ -101,6 +188,23 @@ class FlatAdam(object):
 
     def zero_grad(self, set_to_none=False):      # the reducer owns the gradients
         self.reducer.flat[self.lo:self.hi].zero_()
+
+    def health(self):
+        """What the last step() -- eager or a replay -- saw and decided, in ONE device-to-host copy:
+        {segment name: {"norm", "max_abs", "nonfinite", "n"}} (norm and max_abs over the finite elements) plus "scale" (the clip
+        factor of that step; 0.0 when it was skipped), "skipped" (that step), "steps_skipped", "steps_seen" and "steps_applied".
+        Parameters and moments of a skipped step are untouched; BatchNorm running statistics are not part of the guard."""
+        if not self.guarded:
+            raise RuntimeError("FlatAdam.health() needs monitor, skip_nonfinite or max_grad_norm")
+        host = self._health.cpu().tolist()
+        out = {}
+        for k, (name, _) in enumerate(self.segments):
+            sumsq, max_abs, bad, count = host[4 * k:4 * k + 4]
+            out[name] = {"norm": math.sqrt(sumsq), "max_abs": max_abs, "nonfinite": int(bad), "n": int(count)}
+        skip, scale, skipped, seen = host[4 * len(self.segments):4 * len(self.segments) + 4]
+        out.update({"scale": scale, "skipped": bool(skip), "steps_skipped": int(skipped), "steps_seen": int(seen),
+                    "steps_applied": int(seen) - int(skipped)})
+        return out
 
 
 class FlatSGD(object):

@@ -163,13 +163,40 @@ def _load_state_file(net, path, device):
     net.load_state_dict(sd)
 
 
+def _health_options(who, grad_health, skip_nonfinite, max_grad_norm, flat_adam):
+    """The trainers' three gradient-health arguments as FlatAdam's keywords ({} when all are off)."""
+    if not (grad_health or skip_nonfinite or max_grad_norm is not None):
+        return {}
+    if not flat_adam:
+        raise ValueError("%s: grad_health, skip_nonfinite and max_grad_norm are part of the flat Adam step (csrc/adam.hip, "
+                         "csrc/grad_health.hip): they need flat_adam on a GPU" % who)
+    return {"monitor": bool(grad_health), "skip_nonfinite": bool(skip_nonfinite), "max_grad_norm": max_grad_norm}
+
+
+def _merge_health(who, options, optimizers):
+    if not options:
+        raise RuntimeError("%s.health() needs grad_health, skip_nonfinite or max_grad_norm" % who)
+    from .optim import _HEALTH_KEYS
+    out = {}
+    for label, opt in optimizers:
+        h = opt.health()
+        out[label] = {k: h.pop(k) for k in _HEALTH_KEYS}
+        out.update(h)
+    return out
+
+
 class FFWMTrainer(object):
     def __init__(self, device, world_size=1, seed=0, titers=0, bucket_bytes=64 << 20, warp=None,
                  warp_flipcat=None, ngf=64, capturable=False, fused_spectral_norm=None, batched_losses=True,
                  mfma_wgrad=None, flat_adam=None, fused_bn=None, mfma_fwd=None, fused_l1=None, segmented_backward=False,
-                 force_collectives=False, crop=False, loss_precision="fp32"):
+                 force_collectives=False, crop=False, loss_precision="fp32", grad_health=False, skip_nonfinite=False,
+                 max_grad_norm=None):
         self.device = torch.device(device)
         self.titers = titers
+        # grad_health / skip_nonfinite / max_grad_norm: FlatAdam's monitor, non-finite guard and clip by global norm (optim.py), per
+        # optimizer; health() reads them.  They live in the flat step's kernels: without it they are an error, not a no-op.
+        self.health_options = _health_options("FFWMTrainer", grad_health, skip_nonfinite, max_grad_norm,
+                                              (self.device.type == "cuda") if flat_adam is None else bool(flat_adam))
         # "bf16x3": the frozen 3 x 3 layers of the loss networks that conv.WGS_TABLE names run their 16 Winograd GEMMs on the bf16 MFMA
         # with hi / lo split operands (csrc/conv_winograd_gemm_split.hip), forward and data gradient; "fp32": the step as it was
         if loss_precision not in ("fp32", "bf16x3"):
@@ -355,9 +382,15 @@ class FFWMTrainer(object):
             # parameters, gradients and moments as flat arrays: one streaming kernel per optimizer step (csrc/adam.hip); capturable:
             # the step counter lives on the device
             from .optim import FlatAdam
-            self.opt_F = FlatAdam(flow_params, self.red_G, lr=0.00005, betas=(0.5, 0.999), capturable=cap)
-            self.opt_G = FlatAdam(list(self.netG.parameters()), self.red_G, lr=0.0004, betas=(0.5, 0.999), capturable=cap)
-            self.opt_D = FlatAdam(list(self.netD.parameters()), self.red_D, lr=0.0004, betas=(0.5, 0.999), capturable=cap)
+            hk = dict(self.health_options)
+            # opt_F's two networks in the order the reducer laid them out
+            seg_F = sorted((("flowNetF", self._params_F), ("flowNetB", self._params_B)), key=lambda s: self.red_G.offset[s[1][0]][0])
+            self.opt_F = FlatAdam(flow_params, self.red_G, lr=0.00005, betas=(0.5, 0.999), capturable=cap,
+                                  segments=seg_F if hk else None, **hk)
+            self.opt_G = FlatAdam(list(self.netG.parameters()), self.red_G, lr=0.0004, betas=(0.5, 0.999), capturable=cap,
+                                  segments=[("netG", list(self.netG.parameters()))] if hk else None, **hk)
+            self.opt_D = FlatAdam(list(self.netD.parameters()), self.red_D, lr=0.0004, betas=(0.5, 0.999), capturable=cap,
+                                  segments=[("netD", list(self.netD.parameters()))] if hk else None, **hk)
         else:
             self.opt_F = torch.optim.Adam(flow_params, lr=0.00005, betas=(0.5, 0.999), **kw)
             self.opt_G = torch.optim.Adam(self.netG.parameters(), lr=0.0004, betas=(0.5, 0.999), **kw)
@@ -1062,6 +1095,14 @@ class FFWMTrainer(object):
     def loss_values(self):
         return {k: float(v.detach()) for k, v in self.losses.items()}
 
+    def health(self):
+        """Gradient health of the last step, eager or replayed (needs grad_health, skip_nonfinite or max_grad_norm):
+        {"flowNetF" | "flowNetB" | "netG" | "netD": {"norm", "max_abs", "nonfinite", "n"},
+         "opt_F" | "opt_G" | "opt_D": {"scale", "skipped", "steps_skipped", "steps_seen", "steps_applied"}}.
+        One device-to-host copy per optimizer.  A skipped step left that optimizer's parameters and moments as they were; BatchNorm
+        running statistics, updated by the forward pass, are not part of the guard."""
+        return _merge_health("FFWMTrainer", self.health_options, (("opt_F", self.opt_F), ("opt_G", self.opt_G), ("opt_D", self.opt_D)))
+
     def rank_spread(self):
         """max over the ranks of |weights - rank 0's weights|, per network (0.0 everywhere = the ranks are in lock step).  Two
         collectives per network over its flat parameter vector -- a check for after the first replays of a captured data-parallel step
@@ -1175,9 +1216,12 @@ class FlowNetTrainer(object):
     MODEL_NAMES = ("flowNet",)      # flownet_model.py:24
 
     def __init__(self, device, world_size=1, seed=0, ngf=64, warp=None, fused_regularization=None, bucket_bytes=64 << 20,
-                 routed=None, capturable=False, fused_correctness=False, corr_precision="fp32", fused_landmarks=False, reverse=False):
+                 routed=None, capturable=False, fused_correctness=False, corr_precision="fp32", fused_landmarks=False, reverse=False,
+                 grad_health=False, skip_nonfinite=False, max_grad_norm=None):
         from .losses import MultiAffineRegularizationLoss, MultiScaleLDLoss, PerceptualCorrectness
         self.device = torch.device(device)
+        # FlatAdam's monitor, non-finite guard and clip by global norm (optim.py); the flat step runs on the GPU only
+        self.health_options = _health_options("FlowNetTrainer", grad_health, skip_nonfinite, max_grad_norm, self.device.type == "cuda")
         torch.manual_seed(seed)
         self.warp = warp if warp is not None else WarpNet()
         if warp is None and self.device.type == "cuda":
@@ -1221,7 +1265,9 @@ class FlowNetTrainer(object):
         self.reducer = BucketedGradReducer(params, bucket_bytes=bucket_bytes, gather=True)
         if self.device.type == "cuda":
             from .optim import FlatAdam
-            self.optimizer = FlatAdam(params, self.reducer, lr=0.0004, betas=(0.5, 0.999), capturable=cap)
+            hk = dict(self.health_options)
+            self.optimizer = FlatAdam(params, self.reducer, lr=0.0004, betas=(0.5, 0.999), capturable=cap,
+                                      segments=[("flowNet", params)] if hk else None, **hk)
         else:
             self.optimizer = torch.optim.Adam(params, lr=0.0004, betas=(0.5, 0.999))
         self.losses = {}
@@ -1304,6 +1350,13 @@ class FlowNetTrainer(object):
 
     def loss_values(self):
         return {k: float(v.detach()) for k, v in self.losses.items()}
+
+    def health(self):
+        """Gradient health of the last step, eager or replayed (needs grad_health, skip_nonfinite or max_grad_norm):
+        {"flowNet": {"norm", "max_abs", "nonfinite", "n"}, "optimizer": {"scale", "skipped", "steps_skipped", "steps_seen",
+        "steps_applied"}}.  A skipped step left the parameters and moments as they were; BatchNorm running statistics are not part of
+        the guard."""
+        return _merge_health("FlowNetTrainer", self.health_options, (("optimizer", self.optimizer),))
 
     def save_networks(self, save_dir, epoch):
         """BaseModel.save_networks (models/base_model.py:172-191) for the one network of this model: '<epoch>_net_flowNet.pth',

@@ -29,6 +29,9 @@
  *   ffwm_bias_relu_forward          <- conv bias add + nn.ReLU of VGG19  models/losses.py:398-519
  *   ffwm_adam_step                  <- torch.optim.Adam.step            models/ffwm_model.py:46-49,151-160
  *   ffwm_sgd_step                   <- torch.optim.SGD.step, one group per tensor  lightcnn/finetune.py:74-90
+ *   ffwm_grad_health                <- the total norm of torch.nn.utils.clip_grad_norm_ and an isfinite check, per network (no
+ *                                      counterpart in the reference, whose loop looks at no gradient)
+ *   ffwm_adam_step_guarded          <- clip_grad_norm_ + `if isfinite: optimizer.step()` with the decision on the device
  *   ffwm_softmax_xent               <- nn.CrossEntropyLoss + accuracy(output, target, (1, 5))  lightcnn/finetune.py:109,152-159
  *   ffwm_l1_multi                   <- the w * F.l1_loss(x * m, y * m) terms of backward_G   models/ffwm_model.py:107-139
  *   ffwm_conv2d_wgrad[_tiled]       <- convolution_backward grad_weight of the stride-2 / transposed / small-plane convs
@@ -38,6 +41,8 @@
  *   - dtype: FFWM_F32 or FFWM_F64 (the reference dispatches AT_DISPATCH_FLOATING_TYPES).
  *   - stream: a hipStream_t passed as void* (NULL = the null stream).  Launches are
  *     asynchronous, never synchronise, never allocate; the library keeps no tensor state.
+ *     (One stated exception: ffwm_grad_health reads its segment table back, and waits for the stream, when that stream is
+ *     not being captured.)
  *   - The kernels run on the CURRENT HIP device of the calling thread; the caller selects the
  *     device that owns the pointers (one process per GPU in this project).
  *   - Ownership: the caller allocates every output.  Forward outputs are fully overwritten
@@ -53,6 +58,7 @@
 #ifndef FFWM_HIP_H_
 #define FFWM_HIP_H_
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -662,6 +668,51 @@ int ffwm_adam_step(void* params, const void* grads, void* exp_avg, void* exp_avg
  * "no override" (ABI 4; ABI 3 took 0 for "none", so a schedule that reached 0.0 could not freeze the weights).  Two launches. */
 int ffwm_adam_step_device(void* params, const void* grads, void* exp_avg, void* exp_avg_sq, int64_t n, double lr, double beta1,
                           double beta2, double eps, void* state, int dtype, void* stream);
+
+/* ---- gradient health (csrc/grad_health.hip) and the Adam step it guards (csrc/adam.hip) ---------------------------------------
+ * What torch.nn.utils.clip_grad_norm_ and an `if not torch.isfinite(norm)` in front of optimizer.step() do in an eager loop, with
+ * the numbers and the decision in DEVICE memory, so that both can sit inside a captured step (a replay runs no host code).
+ *
+ * ffwm_grad_health: grads = n float32 values, 16-byte aligned, READ ONLY.  seg_end = n_seg ascending ends in elements, read from
+ * DEVICE memory; at most FFWM_GRAD_HEALTH_MAX_SEGMENTS; the last end is n; every end but the last is a multiple of 4 (a segment starts
+ * on a 16-byte boundary, as every parameter of the reducer's flat array does).  record = 4 * n_seg DEVICE doubles, 16-byte aligned:
+ * for segment s, over its FINITE elements, record[4 s] = sum g^2 and record[4 s + 1] = max |g|; record[4 s + 2] = the count of its
+ * non-finite elements (NaN, +inf, -inf), record[4 s + 3] = its element count.  An empty segment, or one without a finite element,
+ * gives a sum of 0 and a maximum of 0.  Squares and sums are double (1e-30, 1e25 and denormals count with their value).
+ * No atomics: a chunk pass writes one partial per FFWM_GRAD_HEALTH_CHUNK elements of a segment (counted from the segment's start) into
+ * `workspace` (16-byte aligned, at least ffwm_grad_health_workspace_bytes(n, n_seg) bytes; 0 for arguments the call would refuse), a
+ * second pass adds a segment's partials; csrc/grad_health.hip states the order of every sum.  The result is a function of the values
+ * and the table alone: two calls agree bit for bit, whatever the grid.  Only `workspace` and `record` are written.
+ * Refused with FFWM_ERR_ARG: NULL or misaligned pointers, n < 1, n_seg outside 1 .. 16, a workspace that is too small, and a table that
+ * is not as stated.  The table is in device memory: on a stream that is NOT being captured the call copies its 8 * n_seg bytes back and
+ * waits for the stream -- the one entry point that does -- to check it; on a stream that is being captured it cannot, and the kernels
+ * read the table through a clamp (every end into [previous end, n], rounded down to a multiple of 4, the last end n), so that no
+ * table makes a load leave the array.  Two launches, safe to capture. */
+#define FFWM_GRAD_HEALTH_CHUNK 8192
+#define FFWM_GRAD_HEALTH_MAX_SEGMENTS 16
+int ffwm_grad_health(const void* grads, int64_t n, const int64_t* seg_end, int n_seg, void* workspace, size_t workspace_bytes,
+                     void* record, int dtype, void* stream);
+size_t ffwm_grad_health_workspace_bytes(int64_t n, int n_seg);
+
+/* ffwm_adam_step_device behind a guard.  `state` = its 4 doubles with the same meaning (the learning-rate override included).
+ * `record` = what ffwm_grad_health wrote for this range (4 * n_seg doubles).  `guard` = 6 DEVICE doubles, zero at the start:
+ *     guard[0] skip flag of this call        guard[1] scale of this call (a float value; 0 for a skipped call)
+ *     guard[2] steps skipped so far          guard[3] steps seen so far
+ *     guard[4] total sum g^2 of this call    guard[5] total non-finite count of this call
+ * A one-thread kernel adds the segments' sums in segment order and decides:
+ *   skip       skip_nonfinite != 0 and the non-finite count > 0: flag = 1, skipped += 1, state[0..2] untouched (the bias corrections
+ *              do not move); the streaming kernel reads the flag and returns: params, exp_avg, exp_avg_sq stay bit for bit.
+ *   otherwise  the state advances exactly as in ffwm_adam_step_device; scale = 1 when max_norm <= 0, else
+ *              min(1, max_norm / (sqrt(total) + 1e-6)) computed in double and rounded once to float -- the coefficient of
+ *              torch.nn.utils.clip_grad_norm_.  The streaming kernel multiplies each gradient by the float scale in registers (the
+ *              gradient array is not written) and takes the step: with a scale of exactly 1 the result equals
+ *              ffwm_adam_step_device's bit for bit.
+ * max_norm > 0 with skip_nonfinite == 0 is refused with FFWM_ERR_ARG (a clip over a non-finite norm has no meaning).
+ * The guard protects params and both moments; whatever the forward pass of the bad step already wrote (BatchNorm running statistics)
+ * is not restored.  Two launches, safe to capture. */
+int ffwm_adam_step_guarded(void* params, const void* grads, void* exp_avg, void* exp_avg_sq, int64_t n, double lr, double beta1,
+                           double beta2, double eps, void* state, const void* record, int n_seg, double max_norm, int skip_nonfinite,
+                           void* guard, int dtype, void* stream);
 
 /* One SGD-momentum step (torch.optim.SGD with dampening 0 and no Nesterov, as lightcnn/finetune.py:88-90 constructs it) over FLAT
  * float32 arrays of n elements, 16-byte aligned: parameters, gradients and the momentum buffer (start it at zero: that is torch's
