@@ -292,7 +292,9 @@ __device__ __forceinline__ void warp_fwd_lds_body(const float* __restrict__ feat
                 s += nb[1] * w[k][1];
                 s += nb[kWlCols] * w[k][2];
                 s += nb[kWlCols + 1] * w[k][3];
-                v[k] = s;
+                // a pixel without a valid corner has no taps: its lbase is the box's first cell, which holds another pixel's data
+                // (0 x NaN = NaN), so its output is 0 whatever the box holds, as the reference's
+                v[k] = live[k] ? s : static_cast<T>(0);
             }
             store4(op, v);
             if (more) commit(tile[p ^ 1]);
@@ -536,7 +538,9 @@ __device__ __forceinline__ void warp_bwd_flow_lds_body(const float* __restrict__
     T* gf = gflow + static_cast<size_t>(b) * 2 * plane;
 #pragma unroll
     for (int k = 0; k < kWlPix; ++k) {
-        if (pin[k]) {
+        // a pixel without a valid corner adds nothing: its sums are 0 x the first cells of the tile's box (NaN where those are not
+        // finite), and the reference's is 0 whatever feat and grad_output hold
+        if (pin[k] && live[k]) {
             const size_t fo = static_cast<size_t>(y) * W + xb + k;
             atomic_add(gf + fo, (static_cast<T>(Wi) / 2) * gix[k]);
             atomic_add(gf + fo + plane, (static_cast<T>(Hi) / 2) * giy[k]);

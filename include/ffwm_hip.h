@@ -161,7 +161,13 @@ int ffwm_resample2d_backward(const void* input1, const void* input2, const void*
 /* WarpNet: out[b,c,y,x] = grid_sample(feat[B,C,Hi,Wi], flow[B,2,H,W]) bilinear, zeros padding,
  * align_corners=False; flow = normalised absolute coordinates, ch0 = x, ch1 = y.
  * flipcat != 0: out is [B,2C,H,W] = cat(w, flip(w, dim 3)) (one read, two writes instead of
- * grid_sample + flip + cat).  Reference: models/base_networks.py:168-173,326-329. */
+ * grid_sample + flip + cat).  Reference: models/base_networks.py:168-173,326-329.
+ * Non-finite values of feat: a NaN or +-Inf cell reaches exactly the outputs that have it as a VALID corner, a corner of weight 0
+ * included (the reference multiplies); a zero-padded corner is no tap, and a pixel without a valid corner is 0 whatever feat
+ * holds.  (The LDS-staged tiles broke the last clause until the forward got its per-element bounds: such a pixel read the first
+ * four cells of its tile's staged box with weight 0, so a NaN there became a NaN band in the padding.)
+ * Per element |out - exact| <= 2^-19 sum_corners |w s| + the fp32 rounding of the unnormalised coordinate
+ * (tests/sample_forward_bounds.py; the fp32 reference itself: a quarter of that). */
 int ffwm_warp_forward(const void* feat, const void* flow, void* output, int64_t B, int64_t C,
                       int64_t Hi, int64_t Wi, int64_t H, int64_t W, int flipcat, int dtype,
                       void* stream);
@@ -169,7 +175,8 @@ int ffwm_warp_forward(const void* feat, const void* flow, void* output, int64_t 
 /* grad_feat[B,C,Hi,Wi] += ; grad_flow[B,2,H,W] += .  Either may be NULL.  grad_output is
  * [B,C,H,W] or, with flipcat bit 0, [B,2C,H,W].  flipcat bit 1 (value 2, ABI 4): grad_feat is UNINITIALISED memory and is produced
  * whole -- the caller's zero-fill is saved (and, on the owned-tile path of planes beyond LDS, the read of it); grad_flow still
- * accumulates. */
+ * accumulates.  A pixel without a valid corner adds nothing to grad_flow, whatever feat and grad_output hold (the LDS-staged
+ * d(flow) tiles used to add 0 x the first cells of the tile's box: NaN beside a non-finite cell). */
 int ffwm_warp_backward(const void* feat, const void* flow, const void* grad_output,
                        void* grad_feat, void* grad_flow, int64_t B, int64_t C, int64_t Hi,
                        int64_t Wi, int64_t H, int64_t W, int flipcat, int dtype, void* stream);

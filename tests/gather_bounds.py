@@ -224,7 +224,8 @@ def warp_restatement(feat, grid, go, flipcat=False, flip_padded=False):
 
         def corner(yy, xx):
             valid = (yy >= 0) & (yy < Hi) & (xx >= 0) & (xx < Wi)
-            return _gather(planes, yy.clamp(0, Hi - 1), xx.clamp(0, Wi - 1), Wi) * valid.unsqueeze(1)
+            v = _gather(planes, yy.clamp(0, Hi - 1), xx.clamp(0, Wi - 1), Wi)
+            return torch.where(valid.unsqueeze(1), v, torch.zeros_like(v))       # (not v * valid: a padded corner is 0 even beside a NaN cell)
 
         s0, s1, s2, s3 = corner(y0, x0), corner(y0, x0 + 1), corner(y0 + 1, x0), corner(y0 + 1, x0 + 1)
         a0, a1, a2, a3 = s0.abs(), s1.abs(), s2.abs(), s3.abs()

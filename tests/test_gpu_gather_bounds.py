@@ -228,6 +228,26 @@ def test_warp_grad_flow_from_the_shared_pixel_kernel(oracle, grid_kind, flipcat)
     _dead_pixels_are_zero(bound, gl, grid_kind)
 
 
+@pytest.mark.parametrize("flipcat", [False, True])
+def test_warp_grad_flow_lds_dead_pixels_beside_a_nonfinite_cell(oracle, flipcat):
+    """warp_bwd_flow_lds_kernel on the forward yardstick's input (tests/sample_forward_bounds.py): under the `outside` grid of
+    in [1, 3, 96, 130] -> 80 x 129 a tile holds pixels without a valid corner and its staged box starts on a NaN cell.  Those pixels'
+    d_flow is 0 as the reference's (the kernel used to add 0 x NaN), the pixels that sample a non-finite cell are non-finite, and
+    every other pixel meets its bound."""
+    import sample_forward_bounds as sf
+    from ffwm_amd import ops
+    feat, grid, _ = sf.warp_case("grids", "outside", "nonfinite", flipcat)
+    go = gb.grads("signed", (1, 6 if flipcat else 3, 80, 129), 163)
+    bound = gb.warp_flow_bound(feat, grid, go, flipcat)
+    gl = torch.zeros(grid.shape, device=DEV)
+    with _scoped({"warp_fwd_variant": 2}) as rows:
+        ops.warp_backward(feat.to(DEV), grid.to(DEV), go.to(DEV), flipcat, None, gl)
+    _assert_ran(rows, _warp_scope(flipcat))
+    what = "warp lds, nonfinite features, flipcat %d" % flipcat
+    _report(what, bound.check(gl, what=what))
+    _dead_pixels_are_zero(bound, gl, "outside")
+
+
 MULTI = ("multi_wide", "multi_crop", "slab5")
 
 
